@@ -15,11 +15,15 @@ the all-ranks-bit-exact flag (range_coder_rust_amd/shard.py).  `bench.py --gpus 
 N ranks itself (torch.distributed.run on 127.0.0.1, before any GPU call), or runs as one rank of
 an external torchrun whose WORLD_SIZE must equal N.
 
-Extras at every N: the uniform configs[1] load (2^20 chunks per GPU, c = 1, total 256; weak
-scaling) and the adaptive configs[3] model (over 256 and over 128 symbols).  At N = 1 also: the
-histogram / entropy report on the headline's buffers, the container and the host-resident
-(PCIe) legs on the uniform leg's buffers, and a CPU baseline (the C oracle on the host cores,
-rank 0, on a bounded sample of the headline's chunks).
+A plain run does the headline only: set up, warm up, time the steps, check the round trip of
+the timed work, print the result line.  --dump-outputs DIR also writes what the last timed step
+returned (dump_outputs below), so that two builds can be compared output for output.
+
+--full adds the extras.  At every N: the uniform configs[1] load (2^20 chunks per GPU, c = 1,
+total 256; weak scaling) and the adaptive configs[3] model (over 256 and over 128 symbols).  At
+N = 1 also: the histogram / entropy report on the headline's buffers, the container and the
+host-resident (PCIe) legs on the uniform leg's buffers, and a CPU baseline (the C oracle on the
+host cores, rank 0, on a bounded sample of the headline's chunks).
 """
 import argparse
 import json
@@ -48,6 +52,12 @@ def parse():
     p.add_argument("--global-chunks", type=int, default=1 << 20,
                    help="headline (configs[4], strong): chunks sharded over the ranks")
     p.add_argument("--chunk-bytes", type=int, default=65536)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the extras (uniform, adaptive, model build, container, host "
+                        "stream, CPU baseline); the --no-* and --cpu-* options below select "
+                        "among them")
     p.add_argument("--no-uniform", action="store_true", help="skip the uniform configs[1] leg")
     p.add_argument("--no-adaptive", action="store_true", help="skip the adaptive (C4) leg")
     p.add_argument("--no-model-build", action="store_true",
@@ -180,6 +190,50 @@ def run_leg(torch, dist, leg, steps, warmup, world):
     ok = shard.all_ranks_true(ok, dist if world > 1 else None, device=CTRL_DEVICE)
     code_bytes = int(leg.out_len.sum())
     return dict(t=t, enc_ms=enc_ms, dec_ms=dec_ms, ok=ok, code_bytes=code_bytes)
+
+
+DUMP_BYTES = 48_000_000  # --dump-outputs: the .npy files together stay below this
+DUMP_PER_CHUNK = 1 << 20  # ... and hold the per-chunk values of at most this many chunks
+
+
+def sample_chunks(n, count):
+    """`count` of the chunk indices 0..n-1 (all of them when count >= n), ascending: the same
+    sample in every run."""
+    if count >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(n, count, replace=False)).astype(np.int64)
+
+
+def dump_plan(n, L, cap):
+    """--dump-outputs: (chunks whose lengths and flags are written, chunks whose code and decoded
+    bytes are written).  At the default size: every chunk, and 58 of them."""
+    per = sample_chunks(n, DUMP_PER_CHUNK)
+    return per, sample_chunks(n, max(1, (DUMP_BYTES - 16 * len(per)) // (4 * (cap + L))))
+
+
+def dump_outputs(torch, leg, path, rank=0, world=1):
+    """What the leg's last encode and decode returned to their caller, as <path>/<name>.npy
+    (N > 1: <name>.rank<r>.npy, each rank its shard):
+      code_len (float64), encode_flags, decode_flags (float32): per chunk, dump_plan()[0];
+      code_sample [S, slot bytes], decoded_sample [S, L] (float32, one byte per element): the
+      chunks of dump_plan()[1]; code bytes past a chunk's code_len are unspecified in the slot
+      and written as 0."""
+    per, full = dump_plan(leg.n, leg.L, leg.cap)
+    dev = leg.syms.device
+    pi = torch.from_numpy(per).to(dev)
+    ol = leg.out_len[torch.from_numpy(full).to(dev)]
+    code = torch.stack([leg.out[k * leg.cap:(k + 1) * leg.cap] for k in full.tolist()])
+    code = code.masked_fill(torch.arange(leg.cap, device=dev)[None, :] >= ol[:, None], 0)
+    dec = torch.stack([leg.dec[k * leg.L:(k + 1) * leg.L] for k in full.tolist()])
+    arrays = dict(code_len=leg.out_len[pi].cpu().numpy().astype(np.float64),
+                  encode_flags=leg.fenc[pi].cpu().numpy().astype(np.float32),
+                  decode_flags=leg.fdec[pi].cpu().numpy().astype(np.float32),
+                  code_sample=code.cpu().numpy().astype(np.float32),
+                  decoded_sample=dec.cpu().numpy().astype(np.float32))
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def model_build_leg(torch, rc, leg, code_bytes, reps=3):
@@ -437,6 +491,9 @@ def traffic_for(path, key):
 def main():
     args = parse()
     world, rank, local = resolve_world(args)
+    if not args.full:  # a plain run: the headline only
+        args.no_uniform = args.no_adaptive = args.no_model_build = True
+        args.no_container = args.no_host_stream = args.no_cpu_baseline = True
     P = plan(world, rank, args.global_chunks, args.chunks, args.chunk_bytes,
              uniform=not args.no_uniform)
     import torch
@@ -465,6 +522,8 @@ def main():
     bufs = Leg.alloc(torch, torch.device("cuda", gpu), max(n, P["weak_n"]), L)
     leg = Leg(torch, rc, synth, ctx, "zipf", n, L, lo, bufs=bufs)
     res = run_leg(torch, dist, leg, args.steps, args.warmup, world)
+    if args.dump_outputs:  # before the extras, which reuse the headline's buffers
+        dump_outputs(torch, leg, args.dump_outputs, rank, world)
     value = n_all * L * args.steps / res["t"] / 1e9
 
     kern = {"encode": kernel_stats(n * L, res["code_bytes"], res["enc_ms"]),

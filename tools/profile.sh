@@ -3,7 +3,7 @@
 #   gpurun -- 'bash tools/profile.sh r02'
 # then, locally: python tools/pmc_traffic.py gpurun_out/prof_r02 --tag r02 --config zipf
 # (writes profiles/traffic.json and profiles/r02/*, which bench.py and DESIGN.md cite).
-# Each pass is its own rocprofv3 run: kernel trace + stats of the exact default bench command,
+# Each pass is its own rocprofv3 run: kernel trace + stats of the bench with its extras (--full),
 # then counter passes (counters are never combined with trace domains; at most 4 TCC counters
 # per pass): FETCH_SIZE and WRITE_SIZE as MI355X_MICROARCH.md prescribes, the raw TCC->EA
 # request counters by size (which FETCH_SIZE's gfx950 expression folds wrongly: 128-B reads
@@ -28,7 +28,7 @@ PASSES=("FETCH_SIZE" "WRITE_SIZE"
 
 if [ -z "${SKIP_TRACE:-}" ]; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/trace" -o run --output-format csv \
-    -- python3 bench.py > "$O/bench.json" 2> "$O/bench.err"
+    -- python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"
   echo "trace pass done"
 fi
 # the counter passes' workload once without a profiler: its algorithmic bytes per launch
