@@ -55,7 +55,9 @@ typedef int rc_status;
                               input): the reference loops forever                            */
 #define RC_F_BAD_MODEL 64u /* stream API: a (c, cum, total) on which the reference panics — total
                               0 (u64 division by zero, range_coder.rs:38-40), LowerBoundOverflow
-                              (:68-81) or UpperBoundOverflow (upper_bound().unwrap(), :138-146) */
+                              (:68-81) or UpperBoundOverflow (upper_bound().unwrap(), :138-146);
+                              indexed batch calls (rc_*_batch_indexed): a model index >= the
+                              set's n_models (the caller's models[idx] would panic)          */
 #define RC_F_FINISHED 128u /* stream API: encode after Encoder::finish, which consumes the
                               encoder (encoder.rs:40)                                        */
 #define RC_F_TOO_LONG 32u  /* chunk of more than RC_MAX_CHUNK_SYMBOLS symbols: the batch kernels
@@ -150,6 +152,62 @@ rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code_de
                           const uint64_t* code_off_dev, const uint64_t* code_len_dev,
                           uint8_t* syms_out_dev, const uint64_t* sym_off_dev, uint32_t n_chunks,
                           uint32_t* flags_dev);
+
+/* ---- static model sets: a model chosen per symbol (encoder.rs:24-37, decoder.rs:38-54) ----
+ * The reference takes the model on EVERY call, so a caller may code each symbol against another
+ * table (context modelling; side information that picks one of a few quantised CDFs).  A static
+ * model set holds n_models static tables over one alphabet and one total_freq, and the indexed
+ * batch calls take one model index per symbol: symbol i of chunk k is coded exactly as
+ * encoder.encode(&models[idx[i]], sym[i]) and decoded exactly as decoder.decode(&models[idx[i]])
+ * with FreqTable::find_index over that row (including its choice of n_symbols-1 when rfreq >=
+ * total).  Bytes, lengths and flags are bit-identical to the reference arithmetic.
+ *
+ * Accepted when 1 <= n_models <= RC_MAX_SET_MODELS, 1 <= n_symbols <= 256, 256 <= total_freq <=
+ * 65536 (a power of two or not) and every row (c_freq_host / cum_freq_host: n_models x n_symbols,
+ * row-major) passes rc_model_create_static's checks against the shared total_freq; anything else
+ * is RC_E_BAD_MODEL.  Zero-frequency symbols are allowed in a row.  The total is shared and
+ * bounded because that is the small-model regime of the coders: range / total is
+ * then computed once per symbol whatever the row, the decoder's carried hint scale does not
+ * depend on the row, and at most 3 bytes settle per symbol, so the margins of both kernels'
+ * rings hold unchanged.  (Rows with different totals: rescale them, rc_quantize_counts.)
+ *
+ * A set is its own kind of rc_model: the indexed calls take nothing else (RC_E_ARG for a static
+ * or adaptive model), and every other entry point that takes a model returns RC_E_ARG for a set.
+ * Destroy it with rc_model_destroy.                                                          */
+#define RC_MAX_SET_MODELS 64u
+rc_status rc_model_create_static_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                     const uint32_t* c_freq_host,   /* n_models x n_symbols */
+                                     const uint32_t* cum_freq_host, /* likewise */
+                                     uint32_t total_freq, rc_model** out);
+/* rc_encode_batch with a model index per symbol.
+ * idx_dev       one byte per symbol, indexed exactly like the symbols: idx[sym_off[k] + i] is
+ *               the row of symbol i of chunk k.  Any alignment works; fastest when idx_dev is
+ *               congruent to syms_dev modulo 16.
+ * flags_dev     as rc_encode_batch (RC_F_ZERO_FREQ and RC_F_BAD_SYMBOL against the symbol's own
+ *               row, RC_F_CAPACITY with the exact length, RC_F_TOO_LONG), and RC_F_BAD_MODEL for
+ *               an index >= n_models; the first error of a chunk wins (at one symbol the index
+ *               is looked at first).  After a flag the chunk's remaining output is unspecified;
+ *               a flagged chunk never reads or writes outside its slots.
+ * Asynchronous and stream-ordered on the context's stream, like rc_encode_batch.           */
+rc_status rc_encode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_t* syms_dev,
+                                  const uint8_t* idx_dev, const uint64_t* sym_off_dev,
+                                  uint32_t n_chunks, uint8_t* out_dev, const uint64_t* out_off_dev,
+                                  uint64_t* out_len_dev, uint32_t* flags_dev);
+/* rc_decode_batch with a model index per symbol (side information, known before decoding).
+ * idx_dev       as above, indexed like syms_out_dev; fastest when congruent to it modulo 16
+ * flags_dev     as rc_decode_batch (RC_F_TRUNCATED, RC_F_CORRUPT, RC_F_TOO_LONG), and
+ *               RC_F_BAD_MODEL for an index >= n_models; the first error of a chunk wins.
+ * Over-read: the code of a chunk is fetched in whole 64-B aligned segments of the address space,
+ * so up to 63 bytes before code_off[k] and after code_off[k] + code_len[k] may be READ (never
+ * beyond the aligned segment that holds the stream's first or last byte, hence never from an
+ * unmapped page); bytes past the end are consumed only by a decode that is flagged
+ * RC_F_TRUNCATED.  rc_decode_batch reads the same way.  Indexes and symbols are touched inside
+ * [sym_off[k], sym_off[k+1]) only.                                                          */
+rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_t* code_dev,
+                                  const uint64_t* code_off_dev, const uint64_t* code_len_dev,
+                                  const uint8_t* idx_dev, uint8_t* syms_out_dev,
+                                  const uint64_t* sym_off_dev, uint32_t n_chunks,
+                                  uint32_t* flags_dev);
 
 /* ---- synchronous host-memory helpers (stage through device memory, wait for completion;
  *      returns RC_E_CHUNK when any chunk is flagged — flags are still filled in).  Their

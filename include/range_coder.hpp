@@ -11,6 +11,12 @@
 //                             (src/decoder.rs:6-55)       -> rc::Decoder (model read per call)
 //   error::RangeCoderError     (src/error.rs:3-13)       -> rc::RangeCoderError (exception)
 //   (new) batch API                                      -> rc::encode_chunks / decode_chunks
+//   (new) batch API, a model per symbol                  -> rc::ModelSet::encode_chunks /
+//                                                           decode_chunks
+//
+// rc::ModelSet is declared only where <hip/hip_runtime_api.h> can be included: the indexed entry
+// points take device memory alone, so its chunk helpers allocate and copy with the HIP runtime
+// themselves.  Everything else in this header needs the C ABI only and is there either way.
 //
 // Header-only; link with librc_amd.so.  Everything runs on the GPU through the C ABI: there is
 // no CPU implementation of the coder in the product.
@@ -246,6 +252,175 @@ inline std::vector<std::vector<uint8_t>> decode_chunks(
   }
   return res;
 }
+
+#if __has_include(<hip/hip_runtime_api.h>)
+}  // namespace rc
+#include <hip/hip_runtime_api.h>
+namespace rc {
+
+// A static model set (rc_model_create_static_set): K tables over one alphabet and one
+// total_freq, and batch coding with a model chosen per symbol -- symbol i of a chunk is coded as
+// encoder.encode(&models[idx[i]], sym[i]) and decoded as decoder.decode(&models[idx[i]]).  The
+// indexed entry points take device memory only, so the chunk helpers stage through buffers
+// they allocate with the HIP runtime (hence this part needs its header).
+class ModelSet {
+ public:
+  // one chunk: its symbols (encode) or code bytes (decode), and one model index per symbol
+  struct Chunk {
+    std::vector<uint8_t> data, idx;
+  };
+
+  ModelSet(Context& ctx, const std::vector<const PModel*>& models) : ctx_(&ctx) {
+    if (models.empty()) throw RangeCoderError("empty model set", RC_E_BAD_MODEL);
+    n_ = (uint32_t)models[0]->alphabet_count();
+    total_ = models[0]->total_freq();
+    for (const PModel* pm : models) {
+      if (pm->alphabet_count() != n_ || pm->total_freq() != total_)
+        throw RangeCoderError("the models of a set share one alphabet and one total_freq",
+                              RC_E_BAD_MODEL);
+      for (uint32_t i = 0; i < n_; ++i) {
+        c_.push_back(pm->c_freq(i));
+        cum_.push_back(pm->cum_freq(i));
+      }
+    }
+    check(rc_model_create_static_set(ctx.get(), (uint32_t)models.size(), n_, c_.data(),
+                                     cum_.data(), total_, &m_),
+          "rc_model_create_static_set");
+  }
+  ~ModelSet() {
+    if (m_) rc_model_destroy(m_);
+  }
+  ModelSet(const ModelSet&) = delete;
+  ModelSet& operator=(const ModelSet&) = delete;
+  rc_model* get() const { return m_; }
+  Context& ctx() const { return *ctx_; }
+  uint64_t slot_capacity(uint64_t n) const {
+    uint32_t cmin = 0xFFFFFFFFu;
+    for (uint32_t x : c_)
+      if (x && x < cmin) cmin = x;
+    const double bits = std::log2((double)total_ / (double)cmin);
+    return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
+  }
+
+  // Encode many independent chunks, a model per symbol, in one launch.
+  std::vector<std::vector<uint8_t>> encode_chunks(const std::vector<Chunk>& chunks) const {
+    const uint32_t n = (uint32_t)chunks.size();
+    std::vector<uint64_t> sym_off(n + 1, 0), cap(n), out_off(n + 1, 0), out_len(n);
+    std::vector<uint32_t> flags(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (chunks[k].data.size() != chunks[k].idx.size())
+        throw RangeCoderError("chunk " + std::to_string(k) + ": one index per symbol", RC_E_ARG);
+      sym_off[k + 1] = sym_off[k] + chunks[k].data.size();
+      cap[k] = slot_capacity(chunks[k].data.size());
+    }
+    std::vector<uint8_t> syms(sym_off[n] ? sym_off[n] : 1), idx(syms.size());
+    for (uint32_t k = 0; k < n; ++k) {
+      std::copy(chunks[k].data.begin(), chunks[k].data.end(), syms.begin() + sym_off[k]);
+      std::copy(chunks[k].idx.begin(), chunks[k].idx.end(), idx.begin() + sym_off[k]);
+    }
+    DevBuf d_syms(syms), d_idx(idx), d_soff(sym_off), d_len(8ull * n), d_flags(4ull * n);
+    std::vector<uint8_t> out;
+    for (int attempt = 0; attempt < 2 && n; ++attempt) {
+      for (uint32_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + cap[k];
+      DevBuf d_ooff(out_off), d_out(out_off[n] ? out_off[n] : 1);
+      check(rc_encode_batch_indexed(ctx_->get(), m_, d_syms.u8(), d_idx.u8(), d_soff.u64(), n,
+                                    d_out.u8(), d_ooff.u64(), (uint64_t*)d_len.p,
+                                    (uint32_t*)d_flags.p),
+            "rc_encode_batch_indexed");
+      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
+      d_len.download(out_len.data());
+      d_flags.download(flags.data());
+      out.resize(d_out.bytes);
+      d_out.download(out.data());
+      bool retry = false;
+      for (uint32_t k = 0; k < n; ++k)
+        if (flags[k] == RC_F_CAPACITY) {  // exact length is known: retry with it
+          cap[k] = (out_len[k] + 15) & ~(uint64_t)15;
+          retry = true;
+        }
+      if (!retry) break;
+    }
+    std::vector<std::vector<uint8_t>> res(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (flags[k])
+        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
+                              RC_E_CHUNK, flags[k]);
+      res[k].assign(out.begin() + out_off[k], out.begin() + out_off[k] + out_len[k]);
+    }
+    return res;
+  }
+
+  // Decode many independent streams: chunk k gives idx.size() symbols (the count is
+  // out-of-band, sample_impl.rs:113-120), symbol i with model idx[i].
+  std::vector<std::vector<uint8_t>> decode_chunks(const std::vector<Chunk>& chunks) const {
+    const uint32_t n = (uint32_t)chunks.size();
+    std::vector<uint64_t> code_off(n), code_len(n), sym_off(n + 1, 0);
+    std::vector<uint32_t> flags(n);
+    uint64_t tot = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      code_off[k] = tot;
+      code_len[k] = chunks[k].data.size();
+      tot += chunks[k].data.size();
+      sym_off[k + 1] = sym_off[k] + chunks[k].idx.size();
+    }
+    std::vector<uint8_t> code(tot + 16, 0), idx(sym_off[n] ? sym_off[n] : 1), syms(idx.size());
+    for (uint32_t k = 0; k < n; ++k) {
+      std::copy(chunks[k].data.begin(), chunks[k].data.end(), code.begin() + code_off[k]);
+      std::copy(chunks[k].idx.begin(), chunks[k].idx.end(), idx.begin() + sym_off[k]);
+    }
+    if (n) {
+      DevBuf d_code(code), d_idx(idx), d_coff(code_off), d_clen(code_len), d_soff(sym_off),
+          d_syms(syms.size()), d_flags(4ull * n);
+      check(rc_decode_batch_indexed(ctx_->get(), m_, d_code.u8(), d_coff.u64(), d_clen.u64(),
+                                    d_idx.u8(), d_syms.u8(), d_soff.u64(), n,
+                                    (uint32_t*)d_flags.p),
+            "rc_decode_batch_indexed");
+      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
+      d_flags.download(flags.data());
+      d_syms.download(syms.data());
+    }
+    std::vector<std::vector<uint8_t>> res(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (flags[k])
+        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
+                              RC_E_CHUNK, flags[k]);
+      res[k].assign(syms.begin() + sym_off[k], syms.begin() + sym_off[k + 1]);
+    }
+    return res;
+  }
+
+ private:
+  // a device buffer, optionally filled from a host vector (synchronous copies)
+  struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    explicit DevBuf(size_t n) : bytes(n ? n : 1) {
+      if (hipMalloc(&p, bytes) != hipSuccess) throw RangeCoderError("hipMalloc", RC_E_DEVICE);
+    }
+    template <class T>
+    explicit DevBuf(const std::vector<T>& v) : DevBuf(v.size() * sizeof(T)) {
+      if (!v.empty() &&
+          hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(p);
+        throw RangeCoderError("hipMemcpy", RC_E_DEVICE);
+      }
+    }
+    ~DevBuf() { (void)hipFree(p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    void download(void* dst) const {
+      if (hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        throw RangeCoderError("hipMemcpy", RC_E_DEVICE);
+    }
+    uint8_t* u8() const { return (uint8_t*)p; }
+    const uint64_t* u64() const { return (const uint64_t*)p; }
+  };
+  Context* ctx_;
+  rc_model* m_ = nullptr;
+  std::vector<uint32_t> c_, cum_;
+  uint32_t n_ = 0, total_ = 0;
+};
+#endif  // the HIP runtime API header
 
 // RangeCoder (src/range_coder.rs:7-146): the public accessors of a coder state (a snapshot: a
 // stream's state lives with its GPU calls, rc_stream_state)

@@ -7,6 +7,8 @@ from .api import (  # noqa: F401
     slot_capacity, encode_host, decode_host, BadModelError, ByteCount, FinishedError, RangeCoder,
     LowerBoundOverflow, UpperBoundOverflow,
     stream_states, stream_encode_batch, stream_decode_batch, encode_host_multi, decode_host_multi,
+    StaticModelSet, encode_batch_indexed, decode_batch_indexed, encode_chunks_indexed,
+    decode_chunks_indexed,
 )
 from . import synth  # noqa: F401
 from .model_build import build_model, histogram, ideal_bits, quantize_counts  # noqa: F401

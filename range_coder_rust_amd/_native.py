@@ -36,7 +36,9 @@ EXPORTS = (
     "rc_container_pack", "rc_container_info_parse", "rc_container_offsets",
     "rc_stream_encode", "rc_stream_decode", "rc_stream_encode_host", "rc_stream_decode_host",
     "rc_encode_host_multi", "rc_decode_host_multi",
+    "rc_model_create_static_set", "rc_encode_batch_indexed", "rc_decode_batch_indexed",
 )
+MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 RC_E_BAD_CONTAINER = -6
 RC_E_CAPACITY = -7
 CONTAINER_HEADER_BYTES = 64
@@ -122,6 +124,14 @@ def load():
                                         ctypes.POINTER(_U32)]
     L.rc_encode_host_multi.argtypes = [_P, _P, _U32, _P, _P, _U32, _P, _P, _P, _P]
     L.rc_decode_host_multi.argtypes = [_P, _P, _U32, _P, _P, _P, _P, _P, _U32, _P]
+    L.rc_model_create_static_set.argtypes = [_P, _U32, _U32, _P, _P, _U32, ctypes.POINTER(_P)]
+    L.rc_encode_batch_indexed.argtypes = [_P, _P, _P, _P, _P, _U32, _P, _P, _P, _P]
+    L.rc_decode_batch_indexed.argtypes = [_P, _P, _P, _P, _P, _P, _P, _P, _U32, _P]
+    # host-only hooks of the model sets (not in the header; tests/test_model_set.py)
+    L.rc_model_set_check_.argtypes = [_U32, _U32, _P, _P, _U32]
+    L.rc_model_set_check_.restype = _I
+    L.rc_model_set_plan_.argtypes = [_U32, _U32, _P]
+    L.rc_model_set_plan_.restype = _I
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error"):
             getattr(L, name).restype = _I

@@ -37,6 +37,8 @@ __all__ = [
     "LowerBoundOverflow", "UpperBoundOverflow",
     "ByteCount", "encode_host_multi", "decode_host_multi", "stream_states", "stream_encode_batch", "stream_decode_batch", "encode_batch", "decode_batch", "encode_chunks", "decode_chunks",
     "default_context", "flag_names", "slot_capacity",
+    "StaticModelSet", "encode_batch_indexed", "decode_batch_indexed", "encode_chunks_indexed",
+    "decode_chunks_indexed",
 ]
 
 
@@ -386,6 +388,94 @@ class AdaptiveModel:
     __del__ = StaticModel.__del__
 
 
+class StaticModelSet:
+    """rc_model_create_static_set: K static tables (rows) over one alphabet and one total_freq,
+    for the indexed batch calls, which take one row index per symbol (the reference's
+    encode(&models[idx[i]], sym[i]) / decode(&models[idx[i]])).
+
+    c_rows / cum_rows: K x n_symbols.  The rows are validated on the host at construction
+    (ValueError); the device snapshot is made on first use, so a set can be built and inspected
+    without a device."""
+
+    def __init__(self, c_rows, cum_rows=None, total_freq=None, ctx=None):
+        c = np.ascontiguousarray(c_rows, dtype=np.uint32)
+        if c.ndim != 2:
+            raise ValueError("c_rows must be K x n_symbols")
+        if cum_rows is None:
+            cum = np.zeros_like(c)
+            if c.shape[1] > 1:
+                cum[:, 1:] = np.cumsum(c.astype(np.uint64), axis=1)[:, :-1].astype(np.uint32)
+        else:
+            cum = np.ascontiguousarray(cum_rows, dtype=np.uint32)
+        if cum.shape != c.shape:
+            raise ValueError("c_rows and cum_rows differ in shape")
+        if total_freq is None:
+            total_freq = int(np.sum(c[0], dtype=np.uint64)) if c.size else 0
+        self.c, self.cum, self.total = c, cum, int(total_freq)
+        self.n_models, self.n_symbols = int(c.shape[0]), int(c.shape[1])
+        self._ctx = ctx
+        self._handle = None
+        rc = N.load().rc_model_set_check_(self.n_models, self.n_symbols,
+                                          ctypes.c_void_p(c.ctypes.data),
+                                          ctypes.c_void_p(cum.ctypes.data),
+                                          ctypes.c_uint32(self.total & 0xFFFFFFFF))
+        if rc != N.RC_OK or self.total > 0xFFFFFFFF:
+            raise ValueError(
+                f"model set rejected: need 1..{N.MAX_SET_MODELS} rows of 1..256 symbols, one "
+                "total_freq in 256..65536, and in every row cum[0] == 0, cum[i+1] == cum[i] + "
+                "c[i], sum(c) == total_freq")
+
+    @classmethod
+    def from_counts(cls, count_rows, target_total=65536, ctx=None):
+        """One row per histogram, each scaled to target_total with every symbol kept
+        encodable (rc_quantize_counts with RC_Q_ALL_SYMBOLS)."""
+        from .model_build import quantize_counts
+        rows = [quantize_counts(r, target_total, all_symbols=True) for r in count_rows]
+        return cls([r[0] for r in rows], [r[1] for r in rows], int(target_total), ctx=ctx)
+
+    @classmethod
+    def from_pmodels(cls, pmodels, n_symbols=None, ctx=None):
+        """Snapshot PModels (pmodel.rs:6-10) of one alphabet and one total_freq."""
+        pmodels = list(pmodels)
+        if not pmodels:
+            raise ValueError("no models")
+        n = pmodels[0].alphabet_count() if n_symbols is None else int(n_symbols)
+        c = [[p.c_freq(i) for i in range(n)] for p in pmodels]
+        cum = [[p.cum_freq(i) for i in range(n)] for p in pmodels]
+        totals = {int(p.total_freq()) for p in pmodels}
+        if len(totals) != 1:
+            raise ValueError(f"the models of a set share one total_freq, got {sorted(totals)}")
+        return cls(c, cum, totals.pop(), ctx=ctx)
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    @property
+    def handle(self):
+        if self._handle is None:
+            h = ctypes.c_void_p()
+            N.check(self.ctx._lib.rc_model_create_static_set(
+                self.ctx.handle, self.n_models, self.n_symbols,
+                ctypes.c_void_p(self.c.ctypes.data), ctypes.c_void_p(self.cum.ctypes.data),
+                ctypes.c_uint32(self.total), ctypes.byref(h)), "rc_model_create_static_set")
+            self._handle = h
+        return self._handle
+
+    def max_bits_per_symbol(self):
+        nz = self.c[self.c > 0]
+        return math.log2(self.total / float(nz.min()))
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._ctx._lib.rc_model_destroy(self._handle)
+            self._handle = None
+
+    __del__ = StaticModel.__del__
+
+
 # ----------------------------------------------------------------------------- batch API
 def slot_capacity(n_symbols, bits_per_symbol, slack=1.02):
     """A per-chunk output slot size (16-B multiple) for n symbols at a given worst bit cost."""
@@ -505,6 +595,150 @@ def decode_chunks(model, codes, counts, raise_on_error=True):
     syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.uint8, device=dev)
     flags = decode_batch(model, code_d, torch.from_numpy(coff).to(dev),
                          torch.from_numpy(clen).to(dev), syms_d, torch.from_numpy(sym_off).to(dev))
+    fl = flags.cpu().numpy()
+    host = syms_d.cpu().numpy()
+    res = []
+    for k in range(n):
+        if fl[k] and raise_on_error:
+            _raise_for_flag(int(fl[k]), f"chunk {k}")
+        res.append(host[sym_off[k]: sym_off[k + 1]].copy())
+    return res
+
+
+# ------------------------------------------------------------- batch API, a model per symbol
+def encode_batch_indexed(model_set, syms, idx, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch_indexed on torch tensors (async on torch's current stream): encode_batch
+    with idx uint8[...], one row of model_set per symbol, indexed like syms.
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    torch = _torch()
+    _check_dev(syms, "syms", (torch.uint8,))
+    _check_dev(idx, "idx", (torch.uint8,))
+    _check_dev(out, "out", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
+    # (idx is indexed exactly like syms, so a tensor as long as syms covers every read)
+    if idx.numel() < syms.numel():
+        raise ValueError("idx must hold one index per symbol: at least syms.numel() entries")
+    n = sym_off.numel() - 1
+    if out_off.numel() != n + 1:
+        raise ValueError("out_off must have n_chunks + 1 entries")
+    if out_len is None:
+        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=syms.device)
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
+    ctx = model_set.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_encode_batch_indexed(ctx.handle, model_set.handle, _ptr(syms), _ptr(idx),
+                                             _ptr(sym_off), n, _ptr(out), _ptr(out_off),
+                                             _ptr(out_len), _ptr(flags)),
+            "rc_encode_batch_indexed")
+    return out_len[:n], flags[:n]
+
+
+def decode_batch_indexed(model_set, code, code_off, code_len, idx, syms_out, sym_off, flags=None):
+    """rc_decode_batch_indexed on torch tensors (async on torch's current stream): decode_batch
+    with idx uint8[...], one row of model_set per symbol, indexed like syms_out.  Returns flags."""
+    torch = _torch()
+    _check_dev(code, "code", (torch.uint8,))
+    _check_dev(idx, "idx", (torch.uint8,))
+    _check_dev(syms_out, "syms_out", (torch.uint8,))
+    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
+        _check_dev(t, name, (torch.int64, torch.uint64))
+    # (idx is indexed exactly like syms_out, so a tensor as long as syms_out covers every read)
+    if idx.numel() < syms_out.numel():
+        raise ValueError("idx must hold one index per symbol: at least syms_out.numel() entries")
+    n = sym_off.numel() - 1
+    if code_off.numel() < n or code_len.numel() < n:
+        raise ValueError("code_off/code_len need n_chunks entries")
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
+    ctx = model_set.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_decode_batch_indexed(ctx.handle, model_set.handle, _ptr(code),
+                                             _ptr(code_off), _ptr(code_len), _ptr(idx),
+                                             _ptr(syms_out), _ptr(sym_off), n, _ptr(flags)),
+            "rc_decode_batch_indexed")
+    return flags[:n]
+
+
+def _u8_chunk(c):
+    return (np.frombuffer(bytes(c), dtype=np.uint8) if not isinstance(c, np.ndarray)
+            else np.ascontiguousarray(c, dtype=np.uint8))
+
+
+def encode_chunks_indexed(model_set, chunks, raise_on_error=True):
+    """encode_chunks over a list of (symbols, indexes) pairs (bytes / uint8 arrays of equal
+    length), one chunk each: symbol i is coded with row indexes[i].  Returns a list of bytes."""
+    torch = _torch()
+    dev = torch.device("cuda", model_set.ctx.device)
+    pairs = [(_u8_chunk(s), _u8_chunk(x)) for s, x in chunks]
+    n = len(pairs)
+    if n == 0:
+        return []
+    for k, (s, x) in enumerate(pairs):
+        if len(s) != len(x):
+            raise ValueError(f"chunk {k}: {len(s)} symbols, {len(x)} indexes")
+    lens = np.array([len(s) for s, _ in pairs], dtype=np.int64)
+    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
+        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
+                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum(lens)
+    bits = model_set.max_bits_per_symbol()
+    caps = np.array([slot_capacity(int(L), bits) for L in lens], dtype=np.int64)
+    cat = (lambda j: np.concatenate([p[j] for p in pairs]) if sym_off[-1]
+           else np.zeros(1, np.uint8))
+    syms_d = torch.from_numpy(cat(0)).to(dev)
+    idx_d = torch.from_numpy(cat(1)).to(dev)
+    soff_d = torch.from_numpy(sym_off).to(dev)
+    for attempt in range(2):
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        out_off[1:] = np.cumsum(caps)
+        out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
+        out_len, flags = encode_batch_indexed(model_set, syms_d, idx_d, soff_d, out_d,
+                                              torch.from_numpy(out_off).to(dev))
+        fl = flags.cpu().numpy()
+        ol = out_len.cpu().numpy()
+        if attempt == 0 and np.any(fl == N.F_CAPACITY):
+            caps = np.where(fl == N.F_CAPACITY, (ol + 15) // 16 * 16, caps)
+            continue
+        break
+    host = out_d.cpu().numpy()
+    res = []
+    for k in range(n):
+        if fl[k] and raise_on_error:
+            _raise_for_flag(int(fl[k]), f"chunk {k}")
+        res.append(bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]))
+    return res
+
+
+def decode_chunks_indexed(model_set, chunks, raise_on_error=True):
+    """decode_chunks over a list of (code, indexes) pairs: chunk k decodes len(indexes) symbols,
+    symbol i with row indexes[i].  Returns a list of uint8 numpy arrays."""
+    torch = _torch()
+    dev = torch.device("cuda", model_set.ctx.device)
+    n = len(chunks)
+    if n == 0:
+        return []
+    codes = [bytes(c) for c, _ in chunks]
+    idxs = [_u8_chunk(x) for _, x in chunks]
+    clen = np.array([len(c) for c in codes], dtype=np.int64)
+    coff = np.zeros(n, dtype=np.int64)
+    coff[1:] = np.cumsum(clen)[:-1]
+    counts = np.array([len(x) for x in idxs], dtype=np.int64)
+    if int(counts.max()) > N.MAX_CHUNK_SYMBOLS:
+        raise ChunkTooLongError(f"chunk of {int(counts.max())} symbols: the batch API takes at "
+                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum(counts)
+    blob = np.frombuffer(b"".join(codes) + b"\0" * 16, dtype=np.uint8)
+    code_d = torch.from_numpy(blob.copy()).to(dev)
+    idx_d = torch.from_numpy(np.concatenate(idxs) if sym_off[-1]
+                             else np.zeros(1, np.uint8)).to(dev)
+    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.uint8, device=dev)
+    flags = decode_batch_indexed(model_set, code_d, torch.from_numpy(coff).to(dev),
+                                 torch.from_numpy(clen).to(dev), idx_d, syms_d,
+                                 torch.from_numpy(sym_off).to(dev))
     fl = flags.cpu().numpy()
     host = syms_d.cpu().numpy()
     res = []

@@ -275,3 +275,6 @@ RcKnobs rc_knobs_from_env();                      // rc_kernels.hip (rc_ctx_crea
 // resident wave would hold the hardware queue its stream shares with the launch's)
 void rc_svc_yield_all_();
 const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx);  // rc_kernels.hip
+// rc_kernels.hip: true for a static model set (rc_model_create_static_set), which only the
+// indexed batch calls take; every other entry point that takes a model refuses it (RC_E_ARG)
+bool rc_model_is_set_(const rc_model* m);

@@ -16,7 +16,10 @@
 // ------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) u32 l_u32;
 
-#if RC_DEC_DIV == 0  // (scratch -DRC_STAMP builds: one stamp buffer per translation unit)
+// RC_DEC_SHARED_ONLY (rc_indexed.hip): the per-lane machinery alone (code ring, dec_apply,
+// dec_fix, dec_rare), without k_decode_static and its launchers
+#ifdef RC_DEC_SHARED_ONLY
+#elif RC_DEC_DIV == 0  // (scratch -DRC_STAMP builds: one stamp buffer per translation unit)
 #define RC_DEC_TU dec_pow2
 RC_STAMP_DEFINE(dec_pow2)
 #else
@@ -626,6 +629,7 @@ static __device__ __forceinline__ uint4 dec_phase16(D& d, const ModelArgs& m,
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+#ifndef RC_DEC_SHARED_ONLY
 #ifdef RC_DEC_WAVES  // scratch builds: the occupancy the compiler must fit (DESIGN.md §6)
 #define RC_DEC_ATTR __attribute__((amdgpu_waves_per_eu(RC_DEC_WAVES, RC_DEC_WAVES)))
 #else
@@ -895,3 +899,4 @@ size_t rc_static_decode_lds(const ModelArgs& a, int lut3, u32 wgs) {
   return head + rings + extra;
 }
 #endif
+#endif  // RC_DEC_SHARED_ONLY

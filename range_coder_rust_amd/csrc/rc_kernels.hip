@@ -1,6 +1,7 @@
 // rc_kernels.hip — host side of the static-model coder (contexts, models, launches) and the
 // synthetic workload generator.  The kernels: rc_encode.hip, rc_decode.inc (rc_static.h).
 #include "rc_static.h"
+#include "rc_indexed.h"
 
 // ------------------------------------------------------------------------------------------
 // Synthetic workload generator (inputs for bench/tests, generated directly in HBM)
@@ -88,8 +89,12 @@ RcKnobs rc_knobs_from_env() {
 
 const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx) { return ctx->knobs; }
 
+enum { RC_KIND_STATIC = 0, RC_KIND_ADAPTIVE = 1, RC_KIND_SET = 2 };
+
 struct rc_model {
-  int kind;  // 0 static, 1 adaptive
+  int kind;  // 0 static, 1 adaptive, 2 static model set (rc_indexed.h: `set` and `plan`)
+  SetArgs set;
+  SetPlan plan;
   int device;
   int div;
   ModelArgs args;
@@ -99,6 +104,8 @@ struct rc_model {
   u32 period;          // kind 1: as given
   bool complete;       // kind 0: 256 symbols, every c_freq > 0 (no symbol the coder can reject)
 };
+
+bool rc_model_is_set_(const rc_model* m) { return m && m->kind == RC_KIND_SET; }
 
 namespace {
 
@@ -162,6 +169,62 @@ static void div_constants(ModelArgs& a, u32 total) {
   a.magic = ~0ull / (u64)total;
   a.inv_up = 1.0 / (double)total;  // rounded up: inv_up * total >= 1 exactly
   if (std::fma(a.inv_up, (double)total, -1.0) < 0.0) a.inv_up = std::nextafter(a.inv_up, 2.0);
+}
+
+// The decoders' bucket table of a (c, cum, total) table, 2^bits buckets at most: per bucket
+// s0 | s1 << 8 | split << 16 (s0 = the symbol containing the bucket's first frequency, s1 = the
+// next symbol with c > 0 starting inside the bucket, split = its offset, 0xFFFF: none), padded
+// to a power of two with the last bucket (the kernels mask the bucket index)
+static std::vector<u32> bucket_table(u32 n_symbols, const u32* c_freq, const u32* cum_freq,
+                                     u32 total_freq, u32 bits, u32* shift_out) {
+  const u32 bl = bitlen(total_freq - 1);
+  const u32 shift = bl > bits ? bl - bits : 0u;
+  const u32 nb = ((total_freq - 1) >> shift) + 1;
+  std::vector<u32> lt(nb);
+  u32 s = 0;
+  for (u32 b = 0; b < nb; ++b) {
+    const u64 f0 = (u64)b << shift;
+    const u64 f1 = std::min<u64>((u64)(b + 1) << shift, total_freq);
+    while (s + 1 < n_symbols && (u64)cum_freq[s + 1] <= f0) ++s;
+    u32 s1 = s, split = 0xFFFFu;
+    for (u32 t = s + 1; t < n_symbols; ++t) {
+      if ((u64)cum_freq[t] >= f1) break;
+      if (c_freq[t] > 0) {
+        if ((u64)cum_freq[t] - f0 <= 0xFFFFu) {
+          s1 = t;
+          split = (u32)((u64)cum_freq[t] - f0);
+        }
+        break;
+      }
+    }
+    lt[b] = s | (s1 << 8) | (split << 16);
+  }
+  while (lt.size() & (lt.size() - 1)) lt.push_back(lt.back());
+  *shift_out = shift;
+  return lt;
+}
+
+// rc_model_create_static's checks of one row against a given total
+static bool table_ok(u32 n_symbols, const u32* c_freq, const u32* cum_freq, u32 total_freq) {
+  u64 acc = 0;
+  for (u32 i = 0; i < n_symbols; ++i) {
+    if ((u64)cum_freq[i] != acc) return false;
+    acc += c_freq[i];
+  }
+  return acc == (u64)total_freq;
+}
+
+// what rc_model_create_static_set accepts (include/range_coder.h)
+static rc_status set_check(u32 n_models, u32 n_symbols, const u32* c, const u32* cum,
+                           u32 total) {
+  if (!c || !cum) return RC_E_ARG;
+  if (n_models < 1 || n_models > RC_MAX_SET_MODELS || n_symbols < 1 || n_symbols > 256 ||
+      total < 256 || total > 65536)
+    return RC_E_BAD_MODEL;
+  for (u32 j = 0; j < n_models; ++j)
+    if (!table_ok(n_symbols, c + (size_t)j * n_symbols, cum + (size_t)j * n_symbols, total))
+      return RC_E_BAD_MODEL;
+  return RC_OK;
 }
 
 // range / total through the static coders' three range_par_total forms (rc_static.h), under
@@ -266,7 +329,9 @@ rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device) {
 rc_status rc_model_describe_(const rc_model* m, int* kind, int* device, uint32_t* n_symbols,
                              uint32_t* total, const uint32_t** c_host, uint32_t* increment,
                              uint32_t* limit, uint32_t* period) {
-  if (!m) return RC_E_ARG;
+  // (a static model set is neither: its callers, the container writer among them, take
+  // single-table models only)
+  if (!m || (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE)) return RC_E_ARG;
   *kind = m->kind;
   *device = m->device;
   *n_symbols = m->kind == 0 ? m->args.n : m->ap.n;
@@ -325,30 +390,7 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
   // exactly 2^bits entries whenever total > 2048
   const u32 bl = bitlen(total_freq - 1);
   auto bucket_lut = [&](u32 bits, u32* shift_out) {
-    const u32 shift = bl > bits ? bl - bits : 0u;
-    const u32 nb = ((total_freq - 1) >> shift) + 1;
-    std::vector<u32> lt(nb);
-    u32 s = 0;
-    for (u32 b = 0; b < nb; ++b) {
-      const u64 f0 = (u64)b << shift;
-      const u64 f1 = std::min<u64>((u64)(b + 1) << shift, total_freq);
-      while (s + 1 < n_symbols && (u64)cum_freq[s + 1] <= f0) ++s;
-      u32 s1 = s, split = 0xFFFFu;
-      for (u32 t = s + 1; t < n_symbols; ++t) {
-        if ((u64)cum_freq[t] >= f1) break;
-        if (c_freq[t] > 0) {
-          if ((u64)cum_freq[t] - f0 <= 0xFFFFu) {
-            s1 = t;
-            split = (u32)((u64)cum_freq[t] - f0);
-          }
-          break;
-        }
-      }
-      lt[b] = s | (s1 << 8) | (split << 16);
-    }
-    while (lt.size() & (lt.size() - 1)) lt.push_back(lt.back());
-    *shift_out = shift;
-    return lt;
+    return bucket_table(n_symbols, c_freq, cum_freq, total_freq, bits, shift_out);
   };
   a.lut_bits = total_freq <= 65536 ? SM_LUT_BITS : LUT_BITS;
   std::vector<u32> lut = bucket_lut(a.lut_bits, &a.lut_shift);
@@ -462,6 +504,8 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
   a.pair = pair_bytes ? (const u32*)((char*)d + tab_bytes + lut_bytes) : nullptr;
   rc_model* mm = new rc_model;
   mm->kind = 0;
+  mm->set = SetArgs{};
+  mm->plan = SetPlan{};
   mm->device = ctx->device;
   mm->div = pow2 ? DIV_POW2 : DIV_MAGIC;
   mm->args = a;
@@ -520,6 +564,8 @@ rc_status rc_encode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
                           const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
                           const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
   if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  // kinds do not mix: a static model set is coded by the indexed calls only
+  if (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
   if (m->device != ctx->device) return RC_E_ARG;
@@ -542,6 +588,8 @@ rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
                           const uint64_t* code_off, const uint64_t* code_len, uint8_t* syms_out,
                           const uint64_t* sym_off, uint32_t n_chunks, uint32_t* flags) {
   if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  // kinds do not mix: a static model set is coded by the indexed calls only
+  if (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
   if (m->device != ctx->device) return RC_E_ARG;
@@ -561,6 +609,131 @@ rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
           : rc_static_decode_launch_magic(ctx->cur, ctx->knobs, m->args, sm, code, code_off, code_len,
                                           syms_out, sym_off, n_chunks, flags);
   return e == hipSuccess ? RC_OK : device_error(e, "decode launch");
+}
+
+// ---- static model sets (rc_indexed.h; kernels in rc_indexed.hip) ----
+
+// Internal test hooks (not in include/range_coder.h; host only, no device needed).
+// rc_model_set_check_: rc_model_create_static_set's validation of its tables.
+rc_status rc_model_set_check_(uint32_t n_models, uint32_t n_symbols, const uint32_t* c_freq,
+                              const uint32_t* cum_freq, uint32_t total_freq) {
+  return set_check(n_models, n_symbols, c_freq, cum_freq, total_freq);
+}
+// rc_model_set_plan_: what the launchers use for a set of n_models rows of total total_freq (a
+// launch too small to reach every CU with such workgroups runs fewer lanes, rc_indexed.hip),
+// out[8] = encoder {lanes per workgroup, dynamic LDS bytes, table layout (0: 8-B (cum, c)
+// entries, 1: cum-only rows), table bytes}, decoder {lanes, LDS bytes, log2 buckets per row,
+// bucket shift}.
+rc_status rc_model_set_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* out) {
+  if (!out) return RC_E_ARG;
+  if (n_models < 1 || n_models > RC_MAX_SET_MODELS || total_freq < 256 || total_freq > 65536)
+    return RC_E_BAD_MODEL;
+  SetPlan p;
+  rc_set_plan(n_models, total_freq, &p);
+  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
+                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
+  memcpy(out, v, sizeof v);
+  return RC_OK;
+}
+
+rc_status rc_model_create_static_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                     const uint32_t* c_freq, const uint32_t* cum_freq,
+                                     uint32_t total_freq, rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
+  *out = nullptr;
+  const rc_status ok = set_check(n_models, n_symbols, c_freq, cum_freq, total_freq);
+  if (ok != RC_OK) return ok;
+  SetPlan plan;
+  rc_set_plan(n_models, total_freq, &plan);
+  if (!plan.enc_lanes || !plan.dec_lanes) return RC_E_BAD_MODEL;  // unreachable
+  // cum rows, cum[0 .. 256] with the entries from n_symbols on holding the total (so a symbol
+  // past the alphabet has c = 0 in the encoder's cum-only layout), and the rows' buckets
+  // s0 | s1 << 8 | cum[s1] << 16 (s1 = s0 and cum 0 where no symbol starts inside the bucket)
+  const u32 nb = 1u << plan.dec_bits;
+  std::vector<u32> rows((size_t)n_models * SET_ROW_WORDS), lut((size_t)n_models * nb);
+  for (u32 j = 0; j < n_models; ++j) {
+    const u32* c = c_freq + (size_t)j * n_symbols;
+    const u32* cum = cum_freq + (size_t)j * n_symbols;
+    u32* row = rows.data() + (size_t)j * SET_ROW_WORDS;
+    for (u32 s = 0; s < SET_ROW_WORDS; ++s) row[s] = s < n_symbols ? cum[s] : total_freq;
+    u32 shift = 0;
+    const std::vector<u32> lt = bucket_table(n_symbols, c, cum, total_freq, plan.dec_bits, &shift);
+    if (shift != plan.dec_shift || lt.size() > nb) return RC_E_BAD_MODEL;  // unreachable
+    const u32 last = (total_freq - 1) >> shift;  // (padded buckets repeat the last real one)
+    for (u32 b = 0; b < nb; ++b) {
+      const u32 br = std::min(b, last);
+      const u32 e = lt[std::min<size_t>(br, lt.size() - 1)];
+      const u32 split = e >> 16;
+      const u32 cum1 = split == 0xFFFFu ? 0u : (br << shift) + split;
+      lut[(size_t)j * nb + b] = (e & 0xFFFFu) | (cum1 << 16);
+    }
+  }
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  const size_t row_bytes = rows.size() * sizeof(u32), lut_bytes = lut.size() * sizeof(u32);
+  void* d = nullptr;
+  if (hipMalloc(&d, row_bytes + lut_bytes) != hipSuccess) return RC_E_DEVICE;
+  if (hipMemcpy(d, rows.data(), row_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)d + row_bytes, lut.data(), lut_bytes, hipMemcpyHostToDevice) !=
+          hipSuccess) {
+    (void)hipFree(d);
+    return RC_E_DEVICE;
+  }
+  rc_model* mm = new rc_model;
+  memset(mm, 0, sizeof *mm);
+  mm->kind = RC_KIND_SET;
+  mm->device = ctx->device;
+  mm->div = (total_freq & (total_freq - 1)) == 0 ? DIV_POW2 : DIV_MAGIC;
+  mm->dmem = d;
+  mm->plan = plan;
+  SetArgs& a = mm->set;
+  a.m.n = n_symbols;
+  a.m.ftotal = (float)total_freq;
+  div_constants(a.m, total_freq);
+  a.m.lut_bits = plan.dec_bits;
+  a.m.lut_shift = plan.dec_shift;
+  a.rows = (const u32*)d;
+  a.lut = (const u32*)((char*)d + row_bytes);
+  a.k = n_models;
+  a.tab_bytes = plan.enc_tab;
+  *out = mm;
+  return RC_OK;
+}
+
+rc_status rc_encode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_t* syms,
+                                  const uint8_t* idx, const uint64_t* sym_off,
+                                  uint32_t n_chunks, uint8_t* out, const uint64_t* out_off,
+                                  uint64_t* out_len, uint32_t* flags) {
+  if (!ctx || !set || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (set->kind != RC_KIND_SET) return RC_E_ARG;  // kinds do not mix
+  if (n_chunks == 0) return RC_OK;
+  if (!syms || !idx || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
+  if (set->device != ctx->device) return RC_E_ARG;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  rc_svc_yield_all_();
+  const hipError_t e =
+      rc_set_encode_launch(ctx->cur, ctx->knobs, set->set, set->div, set->plan, syms, idx,
+                           sym_off, n_chunks, out, out_off, out_len, flags);
+  return e == hipSuccess ? RC_OK : device_error(e, "indexed encode launch");
+}
+
+rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_t* code,
+                                  const uint64_t* code_off, const uint64_t* code_len,
+                                  const uint8_t* idx, uint8_t* syms_out, const uint64_t* sym_off,
+                                  uint32_t n_chunks, uint32_t* flags) {
+  if (!ctx || !set || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (set->kind != RC_KIND_SET) return RC_E_ARG;  // kinds do not mix
+  if (n_chunks == 0) return RC_OK;
+  if (!code || !code_off || !code_len || !idx || !syms_out || !sym_off || !flags) return RC_E_ARG;
+  if (set->device != ctx->device) return RC_E_ARG;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  rc_svc_yield_all_();
+  const hipError_t e =
+      rc_set_decode_launch(ctx->cur, ctx->knobs, set->set, set->div, set->plan, code, code_off,
+                           code_len, idx, syms_out, sym_off, n_chunks, flags);
+  return e == hipSuccess ? RC_OK : device_error(e, "indexed decode launch");
 }
 
 // rc_encode_host / rc_decode_host: the pipelined host path lives in rc_stream.hip
