@@ -209,6 +209,57 @@ rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_
                                   const uint64_t* sym_off_dev, uint32_t n_chunks,
                                   uint32_t* flags_dev);
 
+/* ---- wide static models: alphabets of 16-bit symbols (pmodel.rs:6-12 indexes with usize) ----
+ * The reference's PModel is indexed with usize and FreqTable::new(alphabet_count) takes any
+ * size; the calls above code one-byte symbols.  A wide static model is one static table over up
+ * to RC_MAX_WIDE_SYMBOLS symbols, and the wide batch calls code 16-bit symbols against it: symbol
+ * i of chunk k is coded exactly as encoder.encode(&table, sym[i]) and decoded exactly as
+ * decoder.decode(&table) with FreqTable::find_index over the table (including its choice of
+ * n_symbols-1 when rfreq >= total and its choice among equal cum values).  Bytes, lengths and
+ * flags are bit-identical to the reference arithmetic.
+ *
+ * Accepted when 1 <= n_symbols <= RC_MAX_WIDE_SYMBOLS, 256 <= total_freq <= 65536 (a power of two
+ * or not) and the table passes rc_model_create_static's checks; anything else is
+ * RC_E_BAD_MODEL.  Zero-frequency symbols are allowed, so n_symbols > total_freq is legal.  The
+ * total is bounded for the same reason as for sets: at most 3 bytes settle per symbol, so the
+ * margins of both kernels' rings and RC_MAX_CHUNK_SYMBOLS hold unchanged.  The cap of 4096 is
+ * where the table still sits in a CU's local memory beside at least 768 chunks' rings in both
+ * directions; larger alphabets need tables outside it and are a later change.
+ *
+ * Symbol buffers hold 16-bit unsigned symbols in host byte order and sym_off counts symbols,
+ * not bytes.  They are declared void pointers; a symbol pointer that is not 2-byte aligned is
+ * RC_E_ARG.
+ *
+ * A wide model is its own kind of rc_model: the wide calls take nothing else (RC_E_ARG for a
+ * static, adaptive or set model), and every other entry point that takes a model returns RC_E_ARG
+ * for a wide model.  Destroy it with rc_model_destroy.                                       */
+#define RC_MAX_WIDE_SYMBOLS 4096u
+rc_status rc_model_create_static_wide(rc_ctx* ctx, uint32_t n_symbols,
+                                      const uint32_t* c_freq_host, const uint32_t* cum_freq_host,
+                                      uint32_t total_freq, rc_model** out);
+/* rc_encode_batch over 16-bit symbols.
+ * syms16_dev    uint16 symbols (index < n_symbols), chunk k = [sym_off[k], sym_off[k+1])
+ * flags_dev     as rc_encode_batch: RC_F_BAD_SYMBOL for any 16-bit value >= n_symbols (65535
+ *               included), RC_F_ZERO_FREQ, RC_F_CAPACITY with the exact length in out_len,
+ *               RC_F_TOO_LONG; the first error of a chunk wins.  After a flag the chunk's
+ *               remaining output is unspecified; a flagged chunk never reads or writes outside
+ *               its slots.
+ * Asynchronous and stream-ordered on the context's stream, like rc_encode_batch.           */
+rc_status rc_encode_batch_wide(rc_ctx* ctx, const rc_model* wide, const void* syms16_dev,
+                               const uint64_t* sym_off_dev, uint32_t n_chunks, uint8_t* out_dev,
+                               const uint64_t* out_off_dev, uint64_t* out_len_dev,
+                               uint32_t* flags_dev);
+/* rc_decode_batch into 16-bit symbols.
+ * syms16_out_dev  uint16 symbols; chunk k gets sym_off[k+1]-sym_off[k] of them
+ * flags_dev     as rc_decode_batch (RC_F_TRUNCATED, also for code_len < 8; RC_F_CORRUPT;
+ *               RC_F_TOO_LONG); the first error of a chunk wins.
+ * Over-read: as rc_decode_batch_indexed (whole 64-B aligned segments of the code).  Symbols are
+ * touched inside [sym_off[k], sym_off[k+1]) only.                                           */
+rc_status rc_decode_batch_wide(rc_ctx* ctx, const rc_model* wide, const uint8_t* code_dev,
+                               const uint64_t* code_off_dev, const uint64_t* code_len_dev,
+                               void* syms16_out_dev, const uint64_t* sym_off_dev,
+                               uint32_t n_chunks, uint32_t* flags_dev);
+
 /* ---- synchronous host-memory helpers (stage through device memory, wait for completion;
  *      returns RC_E_CHUNK when any chunk is flagged — flags are still filled in).  Their
  *      staging buffers (4 x ~2 batches of ~1 GiB, on the context's device) stay allocated
@@ -347,6 +398,11 @@ rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms_dev, const uint64_t* sym
 rc_status rc_quantize_counts(const uint64_t* counts_host, uint32_t n_symbols,
                              uint64_t target_total, uint32_t qflags, uint32_t* c_out_host,
                              uint32_t* cum_out_host, uint32_t* total_out_host);
+/* The same rule for the alphabets of wide static models: n_symbols <= RC_MAX_WIDE_SYMBOLS
+ * (rc_quantize_counts keeps its own limit of 256 and its results).                          */
+rc_status rc_quantize_counts_wide(const uint64_t* counts_host, uint32_t n_symbols,
+                                  uint64_t target_total, uint32_t qflags, uint32_t* c_out_host,
+                                  uint32_t* cum_out_host, uint32_t* total_out_host);
 
 /* Batched PModel::ideal_code_length (pmodel.rs:14-40): bits_dev[k] = sum over symbols s of
  * chunk k of log2(total / c[s]) = sum_i hist[k][i] * (ln total - ln c_i) / ln 2, in f64,

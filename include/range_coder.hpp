@@ -390,6 +390,7 @@ class ModelSet {
   }
 
  private:
+  friend class WideModel;  // (shares DevBuf)
   // a device buffer, optionally filled from a host vector (synchronous copies)
   struct DevBuf {
     void* p = nullptr;
@@ -419,6 +420,154 @@ class ModelSet {
   rc_model* m_ = nullptr;
   std::vector<uint32_t> c_, cum_;
   uint32_t n_ = 0, total_ = 0;
+};
+
+// A wide static model (rc_model_create_static_wide): one table over up to RC_MAX_WIDE_SYMBOLS
+// 16-bit symbols -- the reference's PModel is indexed with usize (pmodel.rs:6-12), and a
+// FreqTable::new(alphabet_count) may hold any number of symbols.  Symbol i of a chunk is coded as
+// encoder.encode(&table, sym[i]) and decoded as decoder.decode(&table).  The wide entry points
+// take device memory only: encode_batch / decode_batch are their typed (uint16_t) forms, and the
+// chunk helpers stage through buffers they allocate with the HIP runtime.
+class WideModel {
+ public:
+  WideModel(Context& ctx, const PModel& pm) : ctx_(&ctx) {
+    const uint32_t n = (uint32_t)pm.alphabet_count();
+    for (uint32_t i = 0; i < n; ++i) {
+      c_.push_back(pm.c_freq(i));
+      cum_.push_back(pm.cum_freq(i));
+    }
+    total_ = pm.total_freq();
+    create();
+  }
+  WideModel(Context& ctx, const std::vector<uint32_t>& c, const std::vector<uint32_t>& cum,
+            uint32_t total)
+      : ctx_(&ctx), c_(c), cum_(cum), total_(total) {
+    if (c.size() != cum.size()) throw RangeCoderError("c and cum differ in length", RC_E_BAD_MODEL);
+    create();
+  }
+  ~WideModel() {
+    if (m_) rc_model_destroy(m_);
+  }
+  WideModel(const WideModel&) = delete;
+  WideModel& operator=(const WideModel&) = delete;
+  rc_model* get() const { return m_; }
+  Context& ctx() const { return *ctx_; }
+  uint64_t slot_capacity(uint64_t n) const {
+    uint32_t cmin = 0xFFFFFFFFu;
+    for (uint32_t x : c_)
+      if (x && x < cmin) cmin = x;
+    const double bits = std::log2((double)total_ / (double)cmin);
+    return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
+  }
+
+  // rc_encode_batch_wide / rc_decode_batch_wide on typed device pointers (asynchronous)
+  void encode_batch(const uint16_t* syms_dev, const uint64_t* sym_off_dev, uint32_t n_chunks,
+                    uint8_t* out_dev, const uint64_t* out_off_dev, uint64_t* out_len_dev,
+                    uint32_t* flags_dev) const {
+    check(rc_encode_batch_wide(ctx_->get(), m_, syms_dev, sym_off_dev, n_chunks, out_dev,
+                               out_off_dev, out_len_dev, flags_dev),
+          "rc_encode_batch_wide");
+  }
+  void decode_batch(const uint8_t* code_dev, const uint64_t* code_off_dev,
+                    const uint64_t* code_len_dev, uint16_t* syms_out_dev,
+                    const uint64_t* sym_off_dev, uint32_t n_chunks, uint32_t* flags_dev) const {
+    check(rc_decode_batch_wide(ctx_->get(), m_, code_dev, code_off_dev, code_len_dev,
+                               syms_out_dev, sym_off_dev, n_chunks, flags_dev),
+          "rc_decode_batch_wide");
+  }
+
+  // Encode many independent chunks of 16-bit symbols in one launch.
+  std::vector<std::vector<uint8_t>> encode_chunks(
+      const std::vector<std::vector<uint16_t>>& chunks) const {
+    typedef ModelSet::DevBuf DevBuf;
+    const uint32_t n = (uint32_t)chunks.size();
+    std::vector<uint64_t> sym_off(n + 1, 0), cap(n), out_off(n + 1, 0), out_len(n);
+    std::vector<uint32_t> flags(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      sym_off[k + 1] = sym_off[k] + chunks[k].size();
+      cap[k] = slot_capacity(chunks[k].size());
+    }
+    std::vector<uint16_t> syms(sym_off[n] ? sym_off[n] : 1);
+    for (uint32_t k = 0; k < n; ++k)
+      std::copy(chunks[k].begin(), chunks[k].end(), syms.begin() + sym_off[k]);
+    DevBuf d_syms(syms), d_soff(sym_off), d_len(8ull * n), d_flags(4ull * n);
+    std::vector<uint8_t> out;
+    for (int attempt = 0; attempt < 2 && n; ++attempt) {
+      for (uint32_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + cap[k];
+      DevBuf d_ooff(out_off), d_out(out_off[n] ? out_off[n] : 1);
+      encode_batch((const uint16_t*)d_syms.p, d_soff.u64(), n, d_out.u8(), d_ooff.u64(),
+                   (uint64_t*)d_len.p, (uint32_t*)d_flags.p);
+      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
+      d_len.download(out_len.data());
+      d_flags.download(flags.data());
+      out.resize(d_out.bytes);
+      d_out.download(out.data());
+      bool retry = false;
+      for (uint32_t k = 0; k < n; ++k)
+        if (flags[k] == RC_F_CAPACITY) {  // exact length is known: retry with it
+          cap[k] = (out_len[k] + 15) & ~(uint64_t)15;
+          retry = true;
+        }
+      if (!retry) break;
+    }
+    std::vector<std::vector<uint8_t>> res(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (flags[k])
+        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
+                              RC_E_CHUNK, flags[k]);
+      res[k].assign(out.begin() + out_off[k], out.begin() + out_off[k] + out_len[k]);
+    }
+    return res;
+  }
+
+  // Decode many independent streams; counts[k] symbols each (out-of-band,
+  // sample_impl.rs:113-120)
+  std::vector<std::vector<uint16_t>> decode_chunks(const std::vector<std::vector<uint8_t>>& codes,
+                                                   const std::vector<uint64_t>& counts) const {
+    typedef ModelSet::DevBuf DevBuf;
+    const uint32_t n = (uint32_t)codes.size();
+    std::vector<uint64_t> code_off(n), code_len(n), sym_off(n + 1, 0);
+    std::vector<uint32_t> flags(n);
+    uint64_t tot = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      code_off[k] = tot;
+      code_len[k] = codes[k].size();
+      tot += codes[k].size();
+      sym_off[k + 1] = sym_off[k] + counts.at(k);
+    }
+    std::vector<uint8_t> code(tot + 16, 0);
+    std::vector<uint16_t> syms(sym_off[n] ? sym_off[n] : 1);
+    for (uint32_t k = 0; k < n; ++k)
+      std::copy(codes[k].begin(), codes[k].end(), code.begin() + code_off[k]);
+    if (n) {
+      DevBuf d_code(code), d_coff(code_off), d_clen(code_len), d_soff(sym_off),
+          d_syms(2 * syms.size()), d_flags(4ull * n);
+      decode_batch(d_code.u8(), d_coff.u64(), d_clen.u64(), (uint16_t*)d_syms.p, d_soff.u64(), n,
+                   (uint32_t*)d_flags.p);
+      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
+      d_flags.download(flags.data());
+      d_syms.download(syms.data());
+    }
+    std::vector<std::vector<uint16_t>> res(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (flags[k])
+        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
+                              RC_E_CHUNK, flags[k]);
+      res[k].assign(syms.begin() + sym_off[k], syms.begin() + sym_off[k + 1]);
+    }
+    return res;
+  }
+
+ private:
+  void create() {
+    check(rc_model_create_static_wide(ctx_->get(), (uint32_t)c_.size(), c_.data(), cum_.data(),
+                                      total_, &m_),
+          "rc_model_create_static_wide");
+  }
+  Context* ctx_;
+  rc_model* m_ = nullptr;
+  std::vector<uint32_t> c_, cum_;
+  uint32_t total_ = 0;
 };
 #endif  // the HIP runtime API header
 

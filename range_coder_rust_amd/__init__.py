@@ -9,9 +9,11 @@ from .api import (  # noqa: F401
     stream_states, stream_encode_batch, stream_decode_batch, encode_host_multi, decode_host_multi,
     StaticModelSet, encode_batch_indexed, decode_batch_indexed, encode_chunks_indexed,
     decode_chunks_indexed,
+    WideStaticModel, encode_batch_wide, decode_batch_wide, encode_chunks_wide,
+    decode_chunks_wide,
 )
 from . import synth  # noqa: F401
-from .model_build import build_model, histogram, ideal_bits, quantize_counts  # noqa: F401
+from .model_build import build_model, histogram, ideal_bits, quantize_counts, quantize_counts_wide  # noqa: F401
 from . import container  # noqa: F401
 from .container import ContainerError, compress, decompress  # noqa: F401
 

@@ -37,8 +37,11 @@ EXPORTS = (
     "rc_stream_encode", "rc_stream_decode", "rc_stream_encode_host", "rc_stream_decode_host",
     "rc_encode_host_multi", "rc_decode_host_multi",
     "rc_model_create_static_set", "rc_encode_batch_indexed", "rc_decode_batch_indexed",
+    "rc_model_create_static_wide", "rc_encode_batch_wide", "rc_decode_batch_wide",
+    "rc_quantize_counts_wide",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
+MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
 RC_E_BAD_CONTAINER = -6
 RC_E_CAPACITY = -7
 CONTAINER_HEADER_BYTES = 64
@@ -132,6 +135,15 @@ def load():
     L.rc_model_set_check_.restype = _I
     L.rc_model_set_plan_.argtypes = [_U32, _U32, _P]
     L.rc_model_set_plan_.restype = _I
+    L.rc_model_create_static_wide.argtypes = [_P, _U32, _P, _P, _U32, ctypes.POINTER(_P)]
+    L.rc_encode_batch_wide.argtypes = [_P, _P, _P, _P, _U32, _P, _P, _P, _P]
+    L.rc_decode_batch_wide.argtypes = [_P, _P, _P, _P, _P, _P, _P, _U32, _P]
+    L.rc_quantize_counts_wide.argtypes = [_P, _U32, _U64, _U32, _P, _P, _P]
+    # host-only hooks of the wide models (not in the header; tests/test_wide_model.py)
+    L.rc_model_wide_check_.argtypes = [_U32, _P, _P, _U32]
+    L.rc_model_wide_check_.restype = _I
+    L.rc_model_wide_plan_.argtypes = [_U32, _U32, _P]
+    L.rc_model_wide_plan_.restype = _I
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error"):
             getattr(L, name).restype = _I

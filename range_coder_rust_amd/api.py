@@ -476,6 +476,81 @@ class StaticModelSet:
     __del__ = StaticModel.__del__
 
 
+class WideStaticModel:
+    """rc_model_create_static_wide: one static table over an alphabet of up to 4096 16-bit
+    symbols (the reference's PModel is indexed with usize), for the wide batch calls, which code
+    uint16 symbols exactly as encode(&table, sym[i]) / decode(&table).
+
+    The table is validated on the host at construction (ValueError); the device snapshot is made
+    on first use, so a model can be built and inspected without a device."""
+
+    def __init__(self, c_freq, cum_freq=None, total_freq=None, ctx=None):
+        c = np.ascontiguousarray(c_freq, dtype=np.uint32)
+        if c.ndim != 1:
+            raise ValueError("c_freq must be one-dimensional")
+        if cum_freq is None:
+            cum = np.zeros_like(c)
+            if len(c) > 1:
+                cum[1:] = np.cumsum(c, dtype=np.uint64)[:-1].astype(np.uint32)
+        else:
+            cum = np.ascontiguousarray(cum_freq, dtype=np.uint32)
+        if cum.shape != c.shape:
+            raise ValueError("c_freq and cum_freq differ in length")
+        if total_freq is None:
+            total_freq = int(np.sum(c, dtype=np.uint64))
+        self.c, self.cum, self.total = c, cum, int(total_freq)
+        self.n_symbols = len(c)
+        self._ctx = ctx
+        self._handle = None
+        rc = N.load().rc_model_wide_check_(self.n_symbols, ctypes.c_void_p(c.ctypes.data),
+                                           ctypes.c_void_p(cum.ctypes.data),
+                                           ctypes.c_uint32(self.total & 0xFFFFFFFF))
+        if rc != N.RC_OK or self.total > 0xFFFFFFFF:
+            raise ValueError(
+                f"wide model rejected: need 1..{N.MAX_WIDE_SYMBOLS} symbols, total_freq in "
+                "256..65536, cum[0] == 0, cum[i+1] == cum[i] + c[i], sum(c) == total_freq")
+
+    @classmethod
+    def from_counts(cls, counts, target_total=65536, ctx=None):
+        """A histogram scaled to target_total with every symbol kept encodable
+        (rc_quantize_counts_wide with RC_Q_ALL_SYMBOLS)."""
+        from .model_build import quantize_counts_wide
+        c, cum, total = quantize_counts_wide(counts, target_total, all_symbols=True)
+        return cls(c, cum, total, ctx=ctx)
+
+    @classmethod
+    def from_pmodel(cls, pmodel, n_symbols=None, ctx=None):
+        """Snapshot any PModel via c_freq/cum_freq/total_freq (pmodel.rs:6-10)."""
+        n = pmodel.alphabet_count() if n_symbols is None else int(n_symbols)
+        c = [pmodel.c_freq(i) for i in range(n)]
+        cum = [pmodel.cum_freq(i) for i in range(n)]
+        return cls(c, cum, pmodel.total_freq(), ctx=ctx)
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = default_context()
+        return self._ctx
+
+    @property
+    def handle(self):
+        if self._handle is None:
+            h = ctypes.c_void_p()
+            N.check(self.ctx._lib.rc_model_create_static_wide(
+                self.ctx.handle, self.n_symbols, ctypes.c_void_p(self.c.ctypes.data),
+                ctypes.c_void_p(self.cum.ctypes.data), ctypes.c_uint32(self.total),
+                ctypes.byref(h)), "rc_model_create_static_wide")
+            self._handle = h
+        return self._handle
+
+    def max_bits_per_symbol(self):
+        nz = self.c[self.c > 0]
+        return math.log2(self.total / float(nz.min()))
+
+    close = StaticModelSet.close
+    __del__ = StaticModel.__del__
+
+
 # ----------------------------------------------------------------------------- batch API
 def slot_capacity(n_symbols, bits_per_symbol, slack=1.02):
     """A per-chunk output slot size (16-B multiple) for n symbols at a given worst bit cost."""
@@ -741,6 +816,142 @@ def decode_chunks_indexed(model_set, chunks, raise_on_error=True):
                                  torch.from_numpy(sym_off).to(dev))
     fl = flags.cpu().numpy()
     host = syms_d.cpu().numpy()
+    res = []
+    for k in range(n):
+        if fl[k] and raise_on_error:
+            _raise_for_flag(int(fl[k]), f"chunk {k}")
+        res.append(host[sym_off[k]: sym_off[k + 1]].copy())
+    return res
+
+
+# --------------------------------------------------------------- batch API, 16-bit symbols
+def _sym16(t, name):
+    """A uint16 symbol tensor (int16 tensors are viewed as uint16: the bits are the symbols)."""
+    torch = _torch()
+    u16 = getattr(torch, "uint16", None)  # (absent from older torch: int16 tensors still work)
+    _check_dev(t, name, (torch.int16,) if u16 is None else (u16, torch.int16))
+    return t
+
+
+def encode_batch_wide(model, syms, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch_wide on torch tensors (async on torch's current stream): encode_batch with
+    syms uint16[...] (int16 is taken as uint16) against a WideStaticModel; sym_off counts symbols.
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    torch = _torch()
+    syms = _sym16(syms, "syms")
+    _check_dev(out, "out", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    if out_off.numel() != n + 1:
+        raise ValueError("out_off must have n_chunks + 1 entries")
+    if out_len is None:
+        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=syms.device)
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
+    ctx = model.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_encode_batch_wide(ctx.handle, model.handle, _ptr(syms), _ptr(sym_off), n,
+                                          _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(flags)),
+            "rc_encode_batch_wide")
+    return out_len[:n], flags[:n]
+
+
+def decode_batch_wide(model, code, code_off, code_len, syms_out, sym_off, flags=None):
+    """rc_decode_batch_wide on torch tensors (async on torch's current stream): decode_batch into
+    syms_out uint16[...] (or int16, written as uint16).  Returns flags."""
+    torch = _torch()
+    _check_dev(code, "code", (torch.uint8,))
+    syms_out = _sym16(syms_out, "syms_out")
+    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
+        _check_dev(t, name, (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    if code_off.numel() < n or code_len.numel() < n:
+        raise ValueError("code_off/code_len need n_chunks entries")
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
+    ctx = model.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_decode_batch_wide(ctx.handle, model.handle, _ptr(code), _ptr(code_off),
+                                          _ptr(code_len), _ptr(syms_out), _ptr(sym_off), n,
+                                          _ptr(flags)), "rc_decode_batch_wide")
+    return flags[:n]
+
+
+def _u16_chunk(c):
+    a = np.asarray(c)
+    if a.size and (a.min() < 0 or a.max() > 0xFFFF):
+        raise BadSymbolError("symbol outside 0..65535")
+    return np.ascontiguousarray(a, dtype=np.uint16).reshape(-1)
+
+
+def encode_chunks_wide(model, chunks, raise_on_error=True):
+    """encode_chunks over a list of 16-bit symbol sequences (uint16 arrays or lists of ints), one
+    chunk each, against a WideStaticModel.  Returns a list of bytes."""
+    torch = _torch()
+    dev = torch.device("cuda", model.ctx.device)
+    arrs = [_u16_chunk(c) for c in chunks]
+    n = len(arrs)
+    if n == 0:
+        return []
+    lens = np.array([len(a) for a in arrs], dtype=np.int64)
+    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
+        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
+                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum(lens)
+    bits = model.max_bits_per_symbol()
+    caps = np.array([slot_capacity(int(L), bits) for L in lens], dtype=np.int64)
+    cat = np.concatenate(arrs) if sym_off[-1] else np.zeros(1, np.uint16)
+    syms_d = torch.from_numpy(cat.view(np.int16)).to(dev)
+    soff_d = torch.from_numpy(sym_off).to(dev)
+    for attempt in range(2):
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        out_off[1:] = np.cumsum(caps)
+        out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
+        out_len, flags = encode_batch_wide(model, syms_d, soff_d, out_d,
+                                           torch.from_numpy(out_off).to(dev))
+        fl = flags.cpu().numpy()
+        ol = out_len.cpu().numpy()
+        if attempt == 0 and np.any(fl == N.F_CAPACITY):
+            caps = np.where(fl == N.F_CAPACITY, (ol + 15) // 16 * 16, caps)
+            continue
+        break
+    host = out_d.cpu().numpy()
+    res = []
+    for k in range(n):
+        if fl[k] and raise_on_error:
+            _raise_for_flag(int(fl[k]), f"chunk {k}")
+        res.append(bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]))
+    return res
+
+
+def decode_chunks_wide(model, codes, counts, raise_on_error=True):
+    """decode_chunks against a WideStaticModel; counts[k] symbols each.  Returns a list of uint16
+    numpy arrays."""
+    torch = _torch()
+    dev = torch.device("cuda", model.ctx.device)
+    n = len(codes)
+    if n == 0:
+        return []
+    codes = [bytes(c) for c in codes]
+    clen = np.array([len(c) for c in codes], dtype=np.int64)
+    coff = np.zeros(n, dtype=np.int64)
+    coff[1:] = np.cumsum(clen)[:-1]
+    counts = np.asarray(counts, dtype=np.int64)
+    if int(counts.max()) > N.MAX_CHUNK_SYMBOLS:
+        raise ChunkTooLongError(f"chunk of {int(counts.max())} symbols: the batch API takes at "
+                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum(counts)
+    blob = np.frombuffer(b"".join(codes) + b"\0" * 16, dtype=np.uint8)
+    code_d = torch.from_numpy(blob.copy()).to(dev)
+    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.int16, device=dev)
+    flags = decode_batch_wide(model, code_d, torch.from_numpy(coff).to(dev),
+                              torch.from_numpy(clen).to(dev), syms_d,
+                              torch.from_numpy(sym_off).to(dev))
+    fl = flags.cpu().numpy()
+    host = syms_d.cpu().numpy().view(np.uint16)
     res = []
     for k in range(n):
         if fl[k] and raise_on_error:

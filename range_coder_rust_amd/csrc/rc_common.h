@@ -278,3 +278,5 @@ const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx);  // rc_kernels.hip
 // rc_kernels.hip: true for a static model set (rc_model_create_static_set), which only the
 // indexed batch calls take; every other entry point that takes a model refuses it (RC_E_ARG)
 bool rc_model_is_set_(const rc_model* m);
+// likewise for a wide static model (rc_model_create_static_wide) and the wide batch calls
+bool rc_model_is_wide_(const rc_model* m);

@@ -43,6 +43,13 @@ struct SetArgs {
   u32 tab_bytes;    // encoder: SetPlan::enc_tab
 };
 
+// shared with the wide coders (rc_wide.hip), whose workgroups are sized the same way:
+// set_allow_lds lets `kernel` take a whole CU's LDS as dynamic LDS; set_launch_lanes gives the
+// lanes per workgroup of a launch of n_chunks chunks (the plan's, or fewer so that a small launch
+// reaches every CU)
+hipError_t set_allow_lds(const void* kernel);
+u32 set_launch_lanes(u32 plan_lanes, u32 n_chunks);
+
 hipError_t rc_set_encode_launch(hipStream_t stream, const RcKnobs& k, const SetArgs& a, int div,
                                 const SetPlan& p, const uint8_t* syms, const uint8_t* idx,
                                 const u64* sym_off, u32 n_chunks, uint8_t* out,

@@ -648,9 +648,9 @@ void rc_set_plan(u32 K, u32 total, SetPlan* p) {
   p->dec_lds = K * (4u * SET_ROW_WORDS + (4u << p->dec_bits)) + best_lanes * SET_DEC_LANE_BYTES;
 }
 
-// The indexed kernels take up to a whole CU's LDS as dynamic LDS: allowed once per (device,
-// kernel), not per launch; a refusal is the launch's error.
-static hipError_t set_allow_lds(const void* kernel) {
+// The indexed kernels (and the wide ones, rc_wide.hip) take up to a whole CU's LDS as dynamic
+// LDS: allowed once per (device, kernel), not per launch; a refusal is the launch's error.
+hipError_t set_allow_lds(const void* kernel) {
   static std::mutex mu;
   static std::set<std::pair<int, const void*>> done;
   int dev = 0;
@@ -667,7 +667,7 @@ static hipError_t set_allow_lds(const void* kernel) {
 // Lanes per workgroup of a launch: the plan's, which is what one CU holds, unless the launch's
 // chunks would then leave CUs idle; then smaller workgroups (never under 256 lanes) so that the
 // grid reaches every CU, each staging the tables for itself.
-static u32 set_launch_lanes(u32 plan_lanes, u32 n_chunks) {
+u32 set_launch_lanes(u32 plan_lanes, u32 n_chunks) {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||

@@ -2,6 +2,7 @@
 // synthetic workload generator.  The kernels: rc_encode.hip, rc_decode.inc (rc_static.h).
 #include "rc_static.h"
 #include "rc_indexed.h"
+#include "rc_wide.h"
 
 // ------------------------------------------------------------------------------------------
 // Synthetic workload generator (inputs for bench/tests, generated directly in HBM)
@@ -89,12 +90,15 @@ RcKnobs rc_knobs_from_env() {
 
 const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx) { return ctx->knobs; }
 
-enum { RC_KIND_STATIC = 0, RC_KIND_ADAPTIVE = 1, RC_KIND_SET = 2 };
+enum { RC_KIND_STATIC = 0, RC_KIND_ADAPTIVE = 1, RC_KIND_SET = 2, RC_KIND_WIDE = 3 };
 
 struct rc_model {
-  int kind;  // 0 static, 1 adaptive, 2 static model set (rc_indexed.h: `set` and `plan`)
+  int kind;  // 0 static, 1 adaptive, 2 static model set (rc_indexed.h: `set` and `plan`),
+             // 3 wide static model (rc_wide.h: `wide` and `wplan`)
   SetArgs set;
   SetPlan plan;
+  WideArgs wide;
+  WidePlan wplan;
   int device;
   int div;
   ModelArgs args;
@@ -106,6 +110,7 @@ struct rc_model {
 };
 
 bool rc_model_is_set_(const rc_model* m) { return m && m->kind == RC_KIND_SET; }
+bool rc_model_is_wide_(const rc_model* m) { return m && m->kind == RC_KIND_WIDE; }
 
 namespace {
 
@@ -329,8 +334,8 @@ rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device) {
 rc_status rc_model_describe_(const rc_model* m, int* kind, int* device, uint32_t* n_symbols,
                              uint32_t* total, const uint32_t** c_host, uint32_t* increment,
                              uint32_t* limit, uint32_t* period) {
-  // (a static model set is neither: its callers, the container writer among them, take
-  // single-table models only)
+  // (a static model set or a wide model is neither: its callers, the container writer among
+  // them, take single-table one-byte models only)
   if (!m || (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE)) return RC_E_ARG;
   *kind = m->kind;
   *device = m->device;
@@ -506,6 +511,8 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
   mm->kind = 0;
   mm->set = SetArgs{};
   mm->plan = SetPlan{};
+  mm->wide = WideArgs{};
+  mm->wplan = WidePlan{};
   mm->device = ctx->device;
   mm->div = pow2 ? DIV_POW2 : DIV_MAGIC;
   mm->args = a;
@@ -564,7 +571,8 @@ rc_status rc_encode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
                           const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
                           const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
   if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  // kinds do not mix: a static model set is coded by the indexed calls only
+  // kinds do not mix: a static model set is coded by the indexed calls only, a wide model by
+  // the wide calls only
   if (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
@@ -588,7 +596,8 @@ rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
                           const uint64_t* code_off, const uint64_t* code_len, uint8_t* syms_out,
                           const uint64_t* sym_off, uint32_t n_chunks, uint32_t* flags) {
   if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  // kinds do not mix: a static model set is coded by the indexed calls only
+  // kinds do not mix: a static model set is coded by the indexed calls only, a wide model by
+  // the wide calls only
   if (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
@@ -795,6 +804,155 @@ rc_status rc_test_range_par_total_(rc_ctx* ctx, const uint64_t* ranges, const ui
   }
   (void)hipFree(d);
   return st;
+}
+
+}  // extern "C"
+
+// ---- wide static models (rc_wide.h; kernels in rc_wide.hip) ----
+
+// what rc_model_create_static_wide accepts (include/range_coder.h)
+static rc_status wide_check(u32 n_symbols, const u32* c, const u32* cum, u32 total) {
+  if (!c || !cum) return RC_E_ARG;
+  if (n_symbols < 1 || n_symbols > RC_MAX_WIDE_SYMBOLS || total < 256 || total > 65536)
+    return RC_E_BAD_MODEL;
+  return table_ok(n_symbols, c, cum, total) ? RC_OK : RC_E_BAD_MODEL;
+}
+
+// The wide decoder's buckets, 2^bits of them: per bucket s_lo | s_hi << 16, FreqTable::find_index
+// of the bucket's first and of its last frequency (the last s with cum[s] <= f; both have c > 0),
+// padded with the last real bucket (the kernel masks the bucket index).  *stride_out: the first
+// stride of the kernel's search, the largest power of two below the widest bucket's symbol count
+// s_hi - s_lo + 1 (0 when every bucket names one symbol).
+static std::vector<u32> wide_buckets(u32 n, const u32* cum, u32 total, u32 bits, u32 shift,
+                                     u32* stride_out) {
+  const u32 nb = 1u << bits, last = (total - 1) >> shift;
+  std::vector<u32> lt(nb);
+  u32 s = 0, widest = 1;
+  auto advance = [&](u32 f) {  // the last s with cum[s] <= f (f rises from call to call)
+    while (s + 1 < n && cum[s + 1] <= f) ++s;
+    return s;
+  };
+  for (u32 b = 0; b <= last && b < nb; ++b) {
+    const u32 f0 = b << shift;
+    const u32 f1 = std::min<u64>((u64)(b + 1) << shift, total);
+    const u32 lo = advance(f0), hi = advance(f1 - 1);
+    lt[b] = lo | (hi << 16);
+    widest = std::max(widest, hi - lo + 1);
+  }
+  for (u32 b = last + 1; b < nb; ++b) lt[b] = lt[last];
+  *stride_out = widest > 1 ? 1u << (bitlen(widest - 1) - 1) : 0u;
+  return lt;
+}
+
+extern "C" {
+
+// Internal test hooks (not in include/range_coder.h; host only, no device needed).
+// rc_model_wide_check_: rc_model_create_static_wide's validation of its table.
+rc_status rc_model_wide_check_(uint32_t n_symbols, const uint32_t* c_freq,
+                               const uint32_t* cum_freq, uint32_t total_freq) {
+  return wide_check(n_symbols, c_freq, cum_freq, total_freq);
+}
+// rc_model_wide_plan_: what the launchers use for a table of n_symbols symbols and total
+// total_freq (a launch too small to reach every CU with such workgroups runs fewer lanes),
+// out[8] = encoder {lanes per workgroup, dynamic LDS bytes, table layout (0: 8-B (cum, c)
+// entries, 1: cum-only row), table bytes}, decoder {lanes, LDS bytes, log2 buckets, bucket shift}.
+rc_status rc_model_wide_plan_(uint32_t n_symbols, uint32_t total_freq, uint32_t* out) {
+  if (!out) return RC_E_ARG;
+  if (n_symbols < 1 || n_symbols > RC_MAX_WIDE_SYMBOLS || total_freq < 256 || total_freq > 65536)
+    return RC_E_BAD_MODEL;
+  WidePlan p;
+  rc_wide_plan(n_symbols, total_freq, &p);
+  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
+                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
+  memcpy(out, v, sizeof v);
+  return RC_OK;
+}
+
+rc_status rc_model_create_static_wide(rc_ctx* ctx, uint32_t n_symbols, const uint32_t* c_freq,
+                                      const uint32_t* cum_freq, uint32_t total_freq,
+                                      rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
+  *out = nullptr;
+  const rc_status ok = wide_check(n_symbols, c_freq, cum_freq, total_freq);
+  if (ok != RC_OK) return ok;
+  WidePlan plan;
+  rc_wide_plan(n_symbols, total_freq, &plan);
+  if (!plan.enc_lanes || !plan.dec_lanes) return RC_E_BAD_MODEL;  // unreachable
+  // the cum row cum[0 .. n + 1] with cum[n] = cum[n + 1] = total (so c = cum[s + 1] - cum[s] for
+  // every symbol, and 0 for the entry a symbol past the alphabet is clamped to), and the buckets
+  std::vector<u32> row(n_symbols + 2);
+  for (u32 s = 0; s < n_symbols + 2; ++s) row[s] = s < n_symbols ? cum_freq[s] : total_freq;
+  u32 top_stride = 0;
+  const std::vector<u32> lut =
+      wide_buckets(n_symbols, cum_freq, total_freq, plan.dec_bits, plan.dec_shift,
+                   &top_stride);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  const size_t row_bytes = row.size() * sizeof(u32), lut_bytes = lut.size() * sizeof(u32);
+  void* d = nullptr;
+  if (hipMalloc(&d, row_bytes + lut_bytes) != hipSuccess) return RC_E_DEVICE;
+  if (hipMemcpy(d, row.data(), row_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)d + row_bytes, lut.data(), lut_bytes, hipMemcpyHostToDevice) !=
+          hipSuccess) {
+    (void)hipFree(d);
+    return RC_E_DEVICE;
+  }
+  rc_model* mm = new rc_model;
+  memset(mm, 0, sizeof *mm);
+  mm->kind = RC_KIND_WIDE;
+  mm->device = ctx->device;
+  mm->div = (total_freq & (total_freq - 1)) == 0 ? DIV_POW2 : DIV_MAGIC;
+  mm->dmem = d;
+  mm->wplan = plan;
+  WideArgs& a = mm->wide;
+  a.m.n = n_symbols;
+  a.m.ftotal = (float)total_freq;
+  div_constants(a.m, total_freq);
+  a.m.lut_bits = plan.dec_bits;
+  a.m.lut_shift = plan.dec_shift;
+  a.row = (const u32*)d;
+  a.lut = (const u32*)((char*)d + row_bytes);
+  a.top_stride = top_stride;
+  a.tab_bytes = plan.enc_tab;
+  *out = mm;
+  return RC_OK;
+}
+
+rc_status rc_encode_batch_wide(rc_ctx* ctx, const rc_model* wide, const void* syms,
+                               const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
+                               const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
+  if (!ctx || !wide || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (wide->kind != RC_KIND_WIDE) return RC_E_ARG;  // kinds do not mix
+  if (((uintptr_t)syms & 1u) != 0) return RC_E_ARG;  // 16-bit symbols
+  if (n_chunks == 0) return RC_OK;
+  if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
+  if (wide->device != ctx->device) return RC_E_ARG;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  rc_svc_yield_all_();
+  const hipError_t e =
+      rc_wide_encode_launch(ctx->cur, ctx->knobs, wide->wide, wide->div, wide->wplan,
+                            (const uint16_t*)syms, sym_off, n_chunks, out, out_off, out_len, flags);
+  return e == hipSuccess ? RC_OK : device_error(e, "wide encode launch");
+}
+
+rc_status rc_decode_batch_wide(rc_ctx* ctx, const rc_model* wide, const uint8_t* code,
+                               const uint64_t* code_off, const uint64_t* code_len,
+                               void* syms_out, const uint64_t* sym_off, uint32_t n_chunks,
+                               uint32_t* flags) {
+  if (!ctx || !wide || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (wide->kind != RC_KIND_WIDE) return RC_E_ARG;  // kinds do not mix
+  if (((uintptr_t)syms_out & 1u) != 0) return RC_E_ARG;  // 16-bit symbols
+  if (n_chunks == 0) return RC_OK;
+  if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
+  if (wide->device != ctx->device) return RC_E_ARG;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  rc_svc_yield_all_();
+  const hipError_t e =
+      rc_wide_decode_launch(ctx->cur, ctx->knobs, wide->wide, wide->div, wide->wplan, code,
+                            code_off, code_len, (uint16_t*)syms_out, sym_off, n_chunks, flags);
+  return e == hipSuccess ? RC_OK : device_error(e, "wide decode launch");
 }
 
 }  // extern "C"

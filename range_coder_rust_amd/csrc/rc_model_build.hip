@@ -231,10 +231,13 @@ rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms, const uint64_t* sym_off
   return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
 }
 
-rc_status rc_quantize_counts(const uint64_t* counts, uint32_t n_symbols, uint64_t target_total,
-                             uint32_t qflags, uint32_t* c_out, uint32_t* cum_out,
-                             uint32_t* total_out) {
-  if (!counts || !c_out || !cum_out || !total_out || n_symbols < 1 || n_symbols > 256)
+}  // extern "C"
+
+// rc_quantize_counts / rc_quantize_counts_wide: one rule, alphabets of up to max_symbols
+static rc_status quantize_counts(const uint64_t* counts, uint32_t n_symbols, u32 max_symbols,
+                                 uint64_t target_total, uint32_t qflags, uint32_t* c_out,
+                                 uint32_t* cum_out, uint32_t* total_out) {
+  if (!counts || !c_out || !cum_out || !total_out || n_symbols < 1 || n_symbols > max_symbols)
     return RC_E_ARG;
   const bool all = (qflags & RC_Q_ALL_SYMBOLS) != 0;
   std::vector<u64> c(n_symbols);
@@ -295,6 +298,21 @@ rc_status rc_quantize_counts(const uint64_t* counts, uint32_t n_symbols, uint64_
   if (acc == 0) return RC_E_BAD_MODEL;
   *total_out = (u32)acc;
   return RC_OK;
+}
+
+extern "C" {
+
+rc_status rc_quantize_counts(const uint64_t* counts, uint32_t n_symbols, uint64_t target_total,
+                             uint32_t qflags, uint32_t* c_out, uint32_t* cum_out,
+                             uint32_t* total_out) {
+  return quantize_counts(counts, n_symbols, 256u, target_total, qflags, c_out, cum_out, total_out);
+}
+
+rc_status rc_quantize_counts_wide(const uint64_t* counts, uint32_t n_symbols,
+                                  uint64_t target_total, uint32_t qflags, uint32_t* c_out,
+                                  uint32_t* cum_out, uint32_t* total_out) {
+  return quantize_counts(counts, n_symbols, RC_MAX_WIDE_SYMBOLS, target_total, qflags, c_out,
+                         cum_out, total_out);
 }
 
 rc_status rc_ideal_bits(rc_ctx* ctx, const uint32_t* c_host, uint32_t n_symbols,

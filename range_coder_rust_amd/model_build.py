@@ -6,6 +6,7 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
 
   histogram(syms, sym_off)        rc_histogram: per-chunk and/or batch symbol counts (HIP)
   quantize_counts(counts, T)      rc_quantize_counts: counts -> (c, cum, total) table
+  quantize_counts_wide(counts, T) the same for up to 4096 symbols (wide static models)
   build_model(syms, sym_off, T)   histogram -> table -> StaticModel, in one call
   ideal_bits(model, chunk_hist)   rc_ideal_bits: per-chunk sum of ideal code lengths (HIP)
 """
@@ -17,7 +18,7 @@ from . import _native as N
 from .api import StaticModel, _check_dev, _ptr, _torch, default_context
 
 
-def quantize_counts(counts, target_total=0, all_symbols=False):
+def quantize_counts(counts, target_total=0, all_symbols=False, _entry="rc_quantize_counts"):
     """rc_quantize_counts (host): counts (len n <= 256) -> (c, cum, total).
 
     target_total 0 keeps calc_cum's exact table; otherwise counts are scaled to that total
@@ -28,14 +29,20 @@ def quantize_counts(counts, target_total=0, all_symbols=False):
     c = np.zeros(max(n, 1), np.uint32)
     cum = np.zeros(max(n, 1), np.uint32)
     total = ctypes.c_uint32()
-    rc = L.rc_quantize_counts(ctypes.c_void_p(cnt.ctypes.data), n, int(target_total),
-                              N.Q_ALL_SYMBOLS if all_symbols else 0,
-                              ctypes.c_void_p(c.ctypes.data), ctypes.c_void_p(cum.ctypes.data),
-                              ctypes.byref(total))
+    rc = getattr(L, _entry)(ctypes.c_void_p(cnt.ctypes.data), n, int(target_total),
+                            N.Q_ALL_SYMBOLS if all_symbols else 0,
+                            ctypes.c_void_p(c.ctypes.data), ctypes.c_void_p(cum.ctypes.data),
+                            ctypes.byref(total))
     if rc == N.RC_E_BAD_MODEL:
         raise ValueError("no frequency table for these counts and target")
-    N.check(rc, "rc_quantize_counts")
+    N.check(rc, _entry)
     return c[:n], cum[:n], int(total.value)
+
+
+def quantize_counts_wide(counts, target_total=0, all_symbols=False):
+    """rc_quantize_counts_wide (host): quantize_counts for the alphabets of wide static models
+    (len n <= 4096)."""
+    return quantize_counts(counts, target_total, all_symbols, _entry="rc_quantize_counts_wide")
 
 
 def histogram(syms, sym_off, per_chunk=False, batch=True, ctx=None):
