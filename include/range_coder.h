@@ -209,6 +209,59 @@ rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_
                                   const uint64_t* sym_off_dev, uint32_t n_chunks,
                                   uint32_t* flags_dev);
 
+/* ---- order-1 sets: the previous symbol picks the model (encoder.rs:24-37, decoder.rs:38-54) ----
+ * The commonest context model: the table of symbol i is chosen by symbol i - 1.  The indexed calls
+ * above can write such a stream (idx[i] = f(sym[i-1])) but not read it back, because the decoder
+ * has no index stream before it has the symbols.  An order-1 set is the K rows of a static model
+ * set (exactly rc_model_create_static_set's rules for n_models, n_symbols, total_freq and the
+ * rows) plus a context map:
+ *   the row of symbol 0 of every chunk is first_row;
+ *   the row of symbol i > 0 is ctx_map[sym[i-1]].
+ * Symbol i of chunk k is coded exactly as encoder.encode(&models[row_i], sym[i]) and decoded
+ * exactly as decoder.decode(&models[row_i]) with FreqTable::find_index over that row (including
+ * its choice of n_symbols-1 when rfreq >= total).  Bytes, lengths and flags are bit-identical to
+ * the reference arithmetic, so the encoder's output is that of rc_encode_batch_indexed fed the
+ * derived index stream; the decoder is what the indexed calls cannot do.
+ *
+ * ctx_map_host: n_symbols bytes, every entry < n_models; first_row < n_models; anything else is
+ * RC_E_BAD_MODEL.  The map is validated here, on the host, so the kernels never meet a bad row
+ * and RC_F_BAD_MODEL cannot occur in the order-1 calls.  n_models <= RC_MAX_SET_MODELS = 64
+ * classes of previous symbol is what fits a CU's local memory beside the chunks' rings; a full
+ * order-1 model of 256 rows does not fit (256 cum rows alone are 257 KiB of the 160 KiB), so
+ * previous symbols are grouped into at most 64 classes by the map.
+ *
+ * An order-1 set is its own kind of rc_model: the order-1 calls take nothing else (RC_E_ARG for a
+ * static, adaptive, set or wide model), and every other entry point that takes a model returns
+ * RC_E_ARG for an order-1 set.  Destroy it with rc_model_destroy.                            */
+rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                     const uint32_t* c_freq_host,   /* n_models x n_symbols */
+                                     const uint32_t* cum_freq_host, /* likewise */
+                                     uint32_t total_freq, const uint8_t* ctx_map_host,
+                                     uint32_t first_row, rc_model** out);
+/* rc_encode_batch with the row chosen by the chunk's previous symbol.
+ * flags_dev     RC_F_BAD_SYMBOL for a symbol >= n_symbols, RC_F_ZERO_FREQ against the row the
+ *               context chose, RC_F_CAPACITY with the exact length in out_len, RC_F_TOO_LONG; the
+ *               first error of a chunk wins.  After a flag the chunk's remaining output is
+ *               unspecified (the symbol after a bad symbol is coded with row 0); a flagged chunk
+ *               never reads or writes outside its slots.
+ * Asynchronous and stream-ordered on the context's stream, like rc_encode_batch.           */
+rc_status rc_encode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms_dev,
+                                 const uint64_t* sym_off_dev, uint32_t n_chunks, uint8_t* out_dev,
+                                 const uint64_t* out_off_dev, uint64_t* out_len_dev,
+                                 uint32_t* flags_dev);
+/* rc_decode_batch with the row chosen by the previous DECODED symbol of the chunk.
+ * flags_dev     as rc_decode_batch_indexed without RC_F_BAD_MODEL: RC_F_TRUNCATED (also for
+ *               code_len < 8, empty chunks included), RC_F_CORRUPT, RC_F_TOO_LONG; the first
+ *               error of a chunk wins.
+ * Over-read: that of rc_decode_batch_indexed (whole 64-B aligned segments of the code: up to 63
+ * bytes before code_off[k] and after code_off[k] + code_len[k] may be READ, never beyond the
+ * aligned segment that holds the stream's first or last byte).  Symbols are touched inside
+ * [sym_off[k], sym_off[k+1]) only.                                                          */
+rc_status rc_decode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* code_dev,
+                                 const uint64_t* code_off_dev, const uint64_t* code_len_dev,
+                                 uint8_t* syms_out_dev, const uint64_t* sym_off_dev,
+                                 uint32_t n_chunks, uint32_t* flags_dev);
+
 /* ---- wide static models: alphabets of 16-bit symbols (pmodel.rs:6-12 indexes with usize) ----
  * The reference's PModel is indexed with usize and FreqTable::new(alphabet_count) takes any
  * size; the calls above code one-byte symbols.  A wide static model is one static table over up
@@ -384,6 +437,17 @@ rc_status rc_synth_fill(rc_ctx* ctx, uint64_t seed, const uint8_t* inv_cdf_host,
  * hist_dev        NULL or 256 uint64: batch counts ADDED into it (zero it first)          */
 rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms_dev, const uint64_t* sym_off_dev,
                        uint32_t n_chunks, uint32_t* chunk_hist_dev, uint64_t* hist_dev);
+
+/* Pair counts by context class: the counts from which the rows of an order-1 set are quantised
+ * (rc_quantize_counts per row, with RC_Q_ALL_SYMBOLS, then rc_model_create_order1_set).
+ * hist_dev: n_models x 256 uint64, ADDED into (zero it first).  Row j counts the symbols of all
+ * chunks whose context row is j under (ctx_map_host, first_row): first_row for the first symbol
+ * of a chunk, ctx_map[previous symbol] for every other one.  Symbols index the map with their
+ * full byte value (ctx_map_host: 256 entries, each < n_models <= RC_MAX_SET_MODELS, and
+ * first_row < n_models; anything else is RC_E_ARG).  Stream-ordered.                        */
+rc_status rc_histogram_order1(rc_ctx* ctx, uint32_t n_models, const uint8_t* ctx_map_host,
+                              uint32_t first_row, const uint8_t* syms_dev,
+                              const uint64_t* sym_off_dev, uint32_t n_chunks, uint64_t* hist_dev);
 
 /* Counts -> (c, cum, total) table (host only, no device needed).
  * target_total == 0: calc_cum's exact table, c = counts (total must stay < 2^32; with

@@ -391,6 +391,7 @@ class ModelSet {
 
  private:
   friend class WideModel;  // (shares DevBuf)
+  friend class Order1Set;
   // a device buffer, optionally filled from a host vector (synchronous copies)
   struct DevBuf {
     void* p = nullptr;
@@ -416,6 +417,142 @@ class ModelSet {
     uint8_t* u8() const { return (uint8_t*)p; }
     const uint64_t* u64() const { return (const uint64_t*)p; }
   };
+  Context* ctx_;
+  rc_model* m_ = nullptr;
+  std::vector<uint32_t> c_, cum_;
+  uint32_t n_ = 0, total_ = 0;
+};
+
+// An order-1 set (rc_model_create_order1_set): K tables over one alphabet and one total_freq
+// plus a context map, and batch coding in which the previous symbol of the chunk picks the
+// table -- symbol 0 of a chunk is coded with models[first_row], symbol i > 0 as
+// encoder.encode(&models[ctx_map[sym[i-1]]], sym[i]), and decoded the same way from the symbols
+// decoded so far.  The order-1 entry points take device memory only, so the chunk helpers stage
+// through buffers they allocate with the HIP runtime.
+class Order1Set {
+ public:
+  // ctx_map: one row per symbol of the alphabet (each < models.size()); first_row likewise
+  Order1Set(Context& ctx, const std::vector<const PModel*>& models,
+            const std::vector<uint8_t>& ctx_map, uint32_t first_row)
+      : ctx_(&ctx) {
+    if (models.empty()) throw RangeCoderError("empty model set", RC_E_BAD_MODEL);
+    n_ = (uint32_t)models[0]->alphabet_count();
+    total_ = models[0]->total_freq();
+    if (ctx_map.size() < n_)
+      throw RangeCoderError("the context map needs one row per symbol", RC_E_BAD_MODEL);
+    for (const PModel* pm : models) {
+      if (pm->alphabet_count() != n_ || pm->total_freq() != total_)
+        throw RangeCoderError("the models of a set share one alphabet and one total_freq",
+                              RC_E_BAD_MODEL);
+      for (uint32_t i = 0; i < n_; ++i) {
+        c_.push_back(pm->c_freq(i));
+        cum_.push_back(pm->cum_freq(i));
+      }
+    }
+    check(rc_model_create_order1_set(ctx.get(), (uint32_t)models.size(), n_, c_.data(),
+                                     cum_.data(), total_, ctx_map.data(), first_row, &m_),
+          "rc_model_create_order1_set");
+  }
+  ~Order1Set() {
+    if (m_) rc_model_destroy(m_);
+  }
+  Order1Set(const Order1Set&) = delete;
+  Order1Set& operator=(const Order1Set&) = delete;
+  rc_model* get() const { return m_; }
+  Context& ctx() const { return *ctx_; }
+  uint64_t slot_capacity(uint64_t n) const {
+    uint32_t cmin = 0xFFFFFFFFu;
+    for (uint32_t x : c_)
+      if (x && x < cmin) cmin = x;
+    const double bits = std::log2((double)total_ / (double)cmin);
+    return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
+  }
+
+  // Encode many independent chunks of symbols in one launch.
+  std::vector<std::vector<uint8_t>> encode_chunks(
+      const std::vector<std::vector<uint8_t>>& chunks) const {
+    using DevBuf = ModelSet::DevBuf;
+    const uint32_t n = (uint32_t)chunks.size();
+    std::vector<uint64_t> sym_off(n + 1, 0), cap(n), out_off(n + 1, 0), out_len(n);
+    std::vector<uint32_t> flags(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      sym_off[k + 1] = sym_off[k] + chunks[k].size();
+      cap[k] = slot_capacity(chunks[k].size());
+    }
+    std::vector<uint8_t> syms(sym_off[n] ? sym_off[n] : 1);
+    for (uint32_t k = 0; k < n; ++k)
+      std::copy(chunks[k].begin(), chunks[k].end(), syms.begin() + sym_off[k]);
+    DevBuf d_syms(syms), d_soff(sym_off), d_len(8ull * n), d_flags(4ull * n);
+    std::vector<uint8_t> out;
+    for (int attempt = 0; attempt < 2 && n; ++attempt) {
+      for (uint32_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + cap[k];
+      DevBuf d_ooff(out_off), d_out(out_off[n] ? out_off[n] : 1);
+      check(rc_encode_batch_order1(ctx_->get(), m_, d_syms.u8(), d_soff.u64(), n, d_out.u8(),
+                                   d_ooff.u64(), (uint64_t*)d_len.p, (uint32_t*)d_flags.p),
+            "rc_encode_batch_order1");
+      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
+      d_len.download(out_len.data());
+      d_flags.download(flags.data());
+      out.resize(d_out.bytes);
+      d_out.download(out.data());
+      bool retry = false;
+      for (uint32_t k = 0; k < n; ++k)
+        if (flags[k] == RC_F_CAPACITY) {  // exact length is known: retry with it
+          cap[k] = (out_len[k] + 15) & ~(uint64_t)15;
+          retry = true;
+        }
+      if (!retry) break;
+    }
+    std::vector<std::vector<uint8_t>> res(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (flags[k])
+        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
+                              RC_E_CHUNK, flags[k]);
+      res[k].assign(out.begin() + out_off[k], out.begin() + out_off[k] + out_len[k]);
+    }
+    return res;
+  }
+
+  // Decode many independent streams: counts[k] symbols from codes[k] (the count is out-of-band,
+  // sample_impl.rs:113-120).
+  std::vector<std::vector<uint8_t>> decode_chunks(const std::vector<std::vector<uint8_t>>& codes,
+                                                  const std::vector<uint64_t>& counts) const {
+    using DevBuf = ModelSet::DevBuf;
+    const uint32_t n = (uint32_t)codes.size();
+    if (counts.size() != n) throw RangeCoderError("one symbol count per stream", RC_E_ARG);
+    std::vector<uint64_t> code_off(n), code_len(n), sym_off(n + 1, 0);
+    std::vector<uint32_t> flags(n);
+    uint64_t tot = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      code_off[k] = tot;
+      code_len[k] = codes[k].size();
+      tot += codes[k].size();
+      sym_off[k + 1] = sym_off[k] + counts[k];
+    }
+    std::vector<uint8_t> code(tot + 16, 0), syms(sym_off[n] ? sym_off[n] : 1);
+    for (uint32_t k = 0; k < n; ++k)
+      std::copy(codes[k].begin(), codes[k].end(), code.begin() + code_off[k]);
+    if (n) {
+      DevBuf d_code(code), d_coff(code_off), d_clen(code_len), d_soff(sym_off),
+          d_syms(syms.size()), d_flags(4ull * n);
+      check(rc_decode_batch_order1(ctx_->get(), m_, d_code.u8(), d_coff.u64(), d_clen.u64(),
+                                   d_syms.u8(), d_soff.u64(), n, (uint32_t*)d_flags.p),
+            "rc_decode_batch_order1");
+      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
+      d_flags.download(flags.data());
+      d_syms.download(syms.data());
+    }
+    std::vector<std::vector<uint8_t>> res(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (flags[k])
+        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
+                              RC_E_CHUNK, flags[k]);
+      res[k].assign(syms.begin() + sym_off[k], syms.begin() + sym_off[k + 1]);
+    }
+    return res;
+  }
+
+ private:
   Context* ctx_;
   rc_model* m_ = nullptr;
   std::vector<uint32_t> c_, cum_;

@@ -11,9 +11,12 @@ from .api import (  # noqa: F401
     decode_chunks_indexed,
     WideStaticModel, encode_batch_wide, decode_batch_wide, encode_chunks_wide,
     decode_chunks_wide,
+    Order1ModelSet, encode_batch_order1, decode_batch_order1, encode_chunks_order1,
+    decode_chunks_order1,
 )
 from . import synth  # noqa: F401
 from .model_build import build_model, histogram, ideal_bits, quantize_counts, quantize_counts_wide  # noqa: F401
+from .model_build import build_order1_set, histogram_order1  # noqa: F401
 from . import container  # noqa: F401
 from .container import ContainerError, compress, decompress  # noqa: F401
 

@@ -39,6 +39,8 @@ EXPORTS = (
     "rc_model_create_static_set", "rc_encode_batch_indexed", "rc_decode_batch_indexed",
     "rc_model_create_static_wide", "rc_encode_batch_wide", "rc_decode_batch_wide",
     "rc_quantize_counts_wide",
+    "rc_model_create_order1_set", "rc_encode_batch_order1", "rc_decode_batch_order1",
+    "rc_histogram_order1",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
@@ -144,6 +146,16 @@ def load():
     L.rc_model_wide_check_.restype = _I
     L.rc_model_wide_plan_.argtypes = [_U32, _U32, _P]
     L.rc_model_wide_plan_.restype = _I
+    L.rc_model_create_order1_set.argtypes = [_P, _U32, _U32, _P, _P, _U32, _P, _U32,
+                                             ctypes.POINTER(_P)]
+    L.rc_encode_batch_order1.argtypes = [_P, _P, _P, _P, _U32, _P, _P, _P, _P]
+    L.rc_decode_batch_order1.argtypes = [_P, _P, _P, _P, _P, _P, _P, _U32, _P]
+    L.rc_histogram_order1.argtypes = [_P, _U32, _P, _U32, _P, _P, _U32, _P]
+    # host-only hooks of the order-1 sets (not in the header; tests/test_order1_model.py)
+    L.rc_model_order1_check_.argtypes = [_U32, _U32, _P, _P, _U32, _P, _U32]
+    L.rc_model_order1_check_.restype = _I
+    L.rc_model_order1_plan_.argtypes = [_U32, _U32, _P]
+    L.rc_model_order1_plan_.restype = _I
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error"):
             getattr(L, name).restype = _I

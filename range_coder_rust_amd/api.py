@@ -39,6 +39,8 @@ __all__ = [
     "default_context", "flag_names", "slot_capacity",
     "StaticModelSet", "encode_batch_indexed", "decode_batch_indexed", "encode_chunks_indexed",
     "decode_chunks_indexed",
+    "Order1ModelSet", "encode_batch_order1", "decode_batch_order1", "encode_chunks_order1",
+    "decode_chunks_order1",
 ]
 
 
@@ -476,6 +478,99 @@ class StaticModelSet:
     __del__ = StaticModel.__del__
 
 
+class Order1ModelSet:
+    """rc_model_create_order1_set: the K rows of a StaticModelSet plus a context map, for the
+    order-1 batch calls, in which the previous symbol of the chunk picks the row: symbol 0 of
+    every chunk is coded with row first_row, symbol i > 0 with row ctx_map[sym[i-1]] (the
+    reference's encode(&models[row_i], sym[i]) / decode(&models[row_i])).
+
+    c_rows / cum_rows: K x n_symbols; ctx_map: at least n_symbols entries, each < K.  Rows, map
+    and first_row are validated on the host at construction (ValueError); the device snapshot is
+    made on first use, so a set can be built and inspected without a device."""
+
+    def __init__(self, c_rows, cum_rows=None, total_freq=None, ctx_map=None, first_row=0,
+                 ctx=None):
+        c = np.ascontiguousarray(c_rows, dtype=np.uint32)
+        if c.ndim != 2:
+            raise ValueError("c_rows must be K x n_symbols")
+        if cum_rows is None:
+            cum = np.zeros_like(c)
+            if c.shape[1] > 1:
+                cum[:, 1:] = np.cumsum(c.astype(np.uint64), axis=1)[:, :-1].astype(np.uint32)
+        else:
+            cum = np.ascontiguousarray(cum_rows, dtype=np.uint32)
+        if cum.shape != c.shape:
+            raise ValueError("c_rows and cum_rows differ in shape")
+        if total_freq is None:
+            total_freq = int(np.sum(c[0], dtype=np.uint64)) if c.size else 0
+        if ctx_map is None:
+            raise ValueError("ctx_map is required: one row per previous symbol")
+        cm = np.asarray(ctx_map)
+        self.n_models, self.n_symbols = int(c.shape[0]), int(c.shape[1])
+        if cm.ndim != 1 or len(cm) < self.n_symbols:
+            raise ValueError(f"ctx_map needs {self.n_symbols} entries, one per symbol")
+        cm = cm[:self.n_symbols].astype(np.int64)
+        first_row = int(first_row)
+        if ((cm < 0) | (cm >= self.n_models)).any() or not 0 <= first_row < max(self.n_models, 1):
+            raise ValueError(f"ctx_map entries and first_row must be rows of the set "
+                             f"(0..{self.n_models - 1})")
+        self.c, self.cum, self.total = c, cum, int(total_freq)
+        self.ctx_map = np.ascontiguousarray(cm, dtype=np.uint8)
+        self.first_row = first_row
+        self._ctx = ctx
+        self._handle = None
+        rc = N.load().rc_model_order1_check_(self.n_models, self.n_symbols,
+                                             ctypes.c_void_p(c.ctypes.data),
+                                             ctypes.c_void_p(cum.ctypes.data),
+                                             ctypes.c_uint32(self.total & 0xFFFFFFFF),
+                                             ctypes.c_void_p(self.ctx_map.ctypes.data),
+                                             ctypes.c_uint32(self.first_row))
+        if rc != N.RC_OK or self.total > 0xFFFFFFFF:
+            raise ValueError(
+                f"order-1 set rejected: need 1..{N.MAX_SET_MODELS} rows of 1..256 symbols, one "
+                "total_freq in 256..65536, in every row cum[0] == 0, cum[i+1] == cum[i] + c[i], "
+                "sum(c) == total_freq, and a ctx_map and first_row that name rows of the set")
+
+    @classmethod
+    def from_counts(cls, count_rows, ctx_map, first_row=0, target_total=65536, ctx=None):
+        """One row per context class from its histogram (rc_histogram_order1's rows), each scaled
+        to target_total with every symbol kept encodable (rc_quantize_counts with
+        RC_Q_ALL_SYMBOLS)."""
+        from .model_build import quantize_counts
+        rows = [quantize_counts(r, target_total, all_symbols=True) for r in count_rows]
+        return cls([r[0] for r in rows], [r[1] for r in rows], int(target_total),
+                   ctx_map=ctx_map, first_row=first_row, ctx=ctx)
+
+    def derive_indexes(self, syms):
+        """The index stream the indexed calls would take for one chunk of symbols (host)."""
+        s = _u8_chunk(syms)
+        idx = np.empty(len(s), np.uint8)
+        if len(s):
+            m = np.zeros(256, np.uint8)
+            m[:self.n_symbols] = self.ctx_map
+            idx[0] = self.first_row
+            idx[1:] = m[s[:-1]]
+        return idx
+
+    ctx = StaticModelSet.ctx
+
+    @property
+    def handle(self):
+        if self._handle is None:
+            h = ctypes.c_void_p()
+            N.check(self.ctx._lib.rc_model_create_order1_set(
+                self.ctx.handle, self.n_models, self.n_symbols,
+                ctypes.c_void_p(self.c.ctypes.data), ctypes.c_void_p(self.cum.ctypes.data),
+                ctypes.c_uint32(self.total), ctypes.c_void_p(self.ctx_map.ctypes.data),
+                ctypes.c_uint32(self.first_row), ctypes.byref(h)), "rc_model_create_order1_set")
+            self._handle = h
+        return self._handle
+
+    max_bits_per_symbol = StaticModelSet.max_bits_per_symbol
+    close = StaticModelSet.close
+    __del__ = StaticModel.__del__
+
+
 class WideStaticModel:
     """rc_model_create_static_wide: one static table over an alphabet of up to 4096 16-bit
     symbols (the reference's PModel is indexed with usize), for the wide batch calls, which code
@@ -814,6 +909,129 @@ def decode_chunks_indexed(model_set, chunks, raise_on_error=True):
     flags = decode_batch_indexed(model_set, code_d, torch.from_numpy(coff).to(dev),
                                  torch.from_numpy(clen).to(dev), idx_d, syms_d,
                                  torch.from_numpy(sym_off).to(dev))
+    fl = flags.cpu().numpy()
+    host = syms_d.cpu().numpy()
+    res = []
+    for k in range(n):
+        if fl[k] and raise_on_error:
+            _raise_for_flag(int(fl[k]), f"chunk {k}")
+        res.append(host[sym_off[k]: sym_off[k + 1]].copy())
+    return res
+
+
+# ------------------------------------------------- batch API, the previous symbol picks the model
+def encode_batch_order1(o1_set, syms, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch_order1 on torch tensors (async on torch's current stream): encode_batch
+    against an Order1ModelSet, the row of each symbol chosen by the chunk's previous symbol.
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    torch = _torch()
+    _check_dev(syms, "syms", (torch.uint8,))
+    _check_dev(out, "out", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    if out_off.numel() != n + 1:
+        raise ValueError("out_off must have n_chunks + 1 entries")
+    if out_len is None:
+        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=syms.device)
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
+    ctx = o1_set.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_encode_batch_order1(ctx.handle, o1_set.handle, _ptr(syms), _ptr(sym_off),
+                                            n, _ptr(out), _ptr(out_off), _ptr(out_len),
+                                            _ptr(flags)), "rc_encode_batch_order1")
+    return out_len[:n], flags[:n]
+
+
+def decode_batch_order1(o1_set, code, code_off, code_len, syms_out, sym_off, flags=None):
+    """rc_decode_batch_order1 on torch tensors (async on torch's current stream): decode_batch
+    against an Order1ModelSet, the row of each symbol chosen by the previous decoded symbol.
+    Returns flags."""
+    torch = _torch()
+    _check_dev(code, "code", (torch.uint8,))
+    _check_dev(syms_out, "syms_out", (torch.uint8,))
+    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
+        _check_dev(t, name, (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    if code_off.numel() < n or code_len.numel() < n:
+        raise ValueError("code_off/code_len need n_chunks entries")
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
+    ctx = o1_set.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_decode_batch_order1(ctx.handle, o1_set.handle, _ptr(code),
+                                            _ptr(code_off), _ptr(code_len), _ptr(syms_out),
+                                            _ptr(sym_off), n, _ptr(flags)),
+            "rc_decode_batch_order1")
+    return flags[:n]
+
+
+def encode_chunks_order1(o1_set, chunks, raise_on_error=True):
+    """encode_chunks over a list of symbol chunks (bytes / uint8 arrays) against an
+    Order1ModelSet.  Returns a list of bytes."""
+    torch = _torch()
+    dev = torch.device("cuda", o1_set.ctx.device)
+    chunks = [_u8_chunk(c) for c in chunks]
+    n = len(chunks)
+    if n == 0:
+        return []
+    lens = np.array([len(c) for c in chunks], dtype=np.int64)
+    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
+        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
+                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum(lens)
+    bits = o1_set.max_bits_per_symbol()
+    caps = np.array([slot_capacity(int(L), bits) for L in lens], dtype=np.int64)
+    syms_d = torch.from_numpy(np.concatenate(chunks) if sym_off[-1]
+                              else np.zeros(1, np.uint8)).to(dev)
+    soff_d = torch.from_numpy(sym_off).to(dev)
+    for attempt in range(2):
+        out_off = np.zeros(n + 1, dtype=np.int64)
+        out_off[1:] = np.cumsum(caps)
+        out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
+        out_len, flags = encode_batch_order1(o1_set, syms_d, soff_d, out_d,
+                                             torch.from_numpy(out_off).to(dev))
+        fl = flags.cpu().numpy()
+        ol = out_len.cpu().numpy()
+        if attempt == 0 and np.any(fl == N.F_CAPACITY):
+            caps = np.where(fl == N.F_CAPACITY, (ol + 15) // 16 * 16, caps)
+            continue
+        break
+    host = out_d.cpu().numpy()
+    res = []
+    for k in range(n):
+        if fl[k] and raise_on_error:
+            _raise_for_flag(int(fl[k]), f"chunk {k}")
+        res.append(bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]))
+    return res
+
+
+def decode_chunks_order1(o1_set, codes, counts, raise_on_error=True):
+    """decode_chunks against an Order1ModelSet: counts[k] symbols from codes[k] (the count is
+    out-of-band, as in the reference).  Returns a list of uint8 numpy arrays."""
+    torch = _torch()
+    dev = torch.device("cuda", o1_set.ctx.device)
+    n = len(codes)
+    if n == 0:
+        return []
+    codes = [bytes(c) for c in codes]
+    clen = np.array([len(c) for c in codes], dtype=np.int64)
+    coff = np.zeros(n, dtype=np.int64)
+    coff[1:] = np.cumsum(clen)[:-1]
+    counts = np.asarray(counts, dtype=np.int64)
+    if int(counts.max()) > N.MAX_CHUNK_SYMBOLS:
+        raise ChunkTooLongError(f"chunk of {int(counts.max())} symbols: the batch API takes at "
+                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum(counts)
+    blob = np.frombuffer(b"".join(codes) + b"\0" * 16, dtype=np.uint8)
+    code_d = torch.from_numpy(blob.copy()).to(dev)
+    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.uint8, device=dev)
+    flags = decode_batch_order1(o1_set, code_d, torch.from_numpy(coff).to(dev),
+                                torch.from_numpy(clen).to(dev), syms_d,
+                                torch.from_numpy(sym_off).to(dev))
     fl = flags.cpu().numpy()
     host = syms_d.cpu().numpy()
     res = []

@@ -280,3 +280,5 @@ const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx);  // rc_kernels.hip
 bool rc_model_is_set_(const rc_model* m);
 // likewise for a wide static model (rc_model_create_static_wide) and the wide batch calls
 bool rc_model_is_wide_(const rc_model* m);
+// likewise for an order-1 set (rc_model_create_order1_set) and the order-1 batch calls
+bool rc_model_is_order1_(const rc_model* m);

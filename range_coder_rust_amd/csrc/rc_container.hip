@@ -302,7 +302,7 @@ rc_status rc_container_pack(rc_ctx* ctx, const rc_model* m, const uint8_t* slots
     return RC_E_ARG;
   if (n_chunks && (!slots_dev || !slot_off_dev || !code_len_dev || !sym_off_dev)) return RC_E_ARG;
   // (RCB1 frames single-table one-byte models only)
-  if (rc_model_is_set_(m) || rc_model_is_wide_(m)) return RC_E_ARG;
+  if (rc_model_is_set_(m) || rc_model_is_wide_(m) || rc_model_is_order1_(m)) return RC_E_ARG;
   int kind, mdev;
   u32 nsym, total, inc, lim, per;
   const u32* c_host;

@@ -2,6 +2,7 @@
 // synthetic workload generator.  The kernels: rc_encode.hip, rc_decode.inc (rc_static.h).
 #include "rc_static.h"
 #include "rc_indexed.h"
+#include "rc_order1.h"
 #include "rc_wide.h"
 
 // ------------------------------------------------------------------------------------------
@@ -90,15 +91,23 @@ RcKnobs rc_knobs_from_env() {
 
 const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx) { return ctx->knobs; }
 
-enum { RC_KIND_STATIC = 0, RC_KIND_ADAPTIVE = 1, RC_KIND_SET = 2, RC_KIND_WIDE = 3 };
+enum {
+  RC_KIND_STATIC = 0,
+  RC_KIND_ADAPTIVE = 1,
+  RC_KIND_SET = 2,
+  RC_KIND_WIDE = 3,
+  RC_KIND_ORDER1 = 4
+};
 
 struct rc_model {
   int kind;  // 0 static, 1 adaptive, 2 static model set (rc_indexed.h: `set` and `plan`),
-             // 3 wide static model (rc_wide.h: `wide` and `wplan`)
+             // 3 wide static model (rc_wide.h: `wide` and `wplan`), 4 order-1 set (rc_order1.h:
+             // `o1` and `plan`)
   SetArgs set;
   SetPlan plan;
   WideArgs wide;
   WidePlan wplan;
+  O1Args o1;
   int device;
   int div;
   ModelArgs args;
@@ -111,6 +120,7 @@ struct rc_model {
 
 bool rc_model_is_set_(const rc_model* m) { return m && m->kind == RC_KIND_SET; }
 bool rc_model_is_wide_(const rc_model* m) { return m && m->kind == RC_KIND_WIDE; }
+bool rc_model_is_order1_(const rc_model* m) { return m && m->kind == RC_KIND_ORDER1; }
 
 namespace {
 
@@ -513,6 +523,7 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
   mm->plan = SetPlan{};
   mm->wide = WideArgs{};
   mm->wplan = WidePlan{};
+  mm->o1 = O1Args{};
   mm->device = ctx->device;
   mm->div = pow2 ? DIV_POW2 : DIV_MAGIC;
   mm->args = a;
@@ -645,15 +656,12 @@ rc_status rc_model_set_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* o
   return RC_OK;
 }
 
-rc_status rc_model_create_static_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
-                                     const uint32_t* c_freq, const uint32_t* cum_freq,
-                                     uint32_t total_freq, rc_model** out) {
-  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
-  *out = nullptr;
-  const rc_status ok = set_check(n_models, n_symbols, c_freq, cum_freq, total_freq);
-  if (ok != RC_OK) return ok;
-  SetPlan plan;
-  rc_set_plan(n_models, total_freq, &plan);
+// The device snapshot of a checked set for `plan` (rc_set_plan's, or rc_order1_plan's with
+// map256: the 256 context-map bytes of an order-1 set, kept behind the tables)
+static rc_status set_build(rc_ctx* ctx, int kind, uint32_t n_models, uint32_t n_symbols,
+                           const uint32_t* c_freq, const uint32_t* cum_freq, uint32_t total_freq,
+                           const SetPlan& plan, const uint8_t* map256, uint32_t first_row,
+                           rc_model** out) {
   if (!plan.enc_lanes || !plan.dec_lanes) return RC_E_BAD_MODEL;  // unreachable
   // cum rows, cum[0 .. 256] with the entries from n_symbols on holding the total (so a symbol
   // past the alphabet has c = 0 in the encoder's cum-only layout), and the rows' buckets
@@ -680,22 +688,25 @@ rc_status rc_model_create_static_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_
   DeviceGuard g(ctx->device);
   if (!g.ok) return RC_E_DEVICE;
   const size_t row_bytes = rows.size() * sizeof(u32), lut_bytes = lut.size() * sizeof(u32);
+  const size_t map_bytes = map256 ? 256 : 0;
   void* d = nullptr;
-  if (hipMalloc(&d, row_bytes + lut_bytes) != hipSuccess) return RC_E_DEVICE;
+  if (hipMalloc(&d, row_bytes + lut_bytes + map_bytes) != hipSuccess) return RC_E_DEVICE;
   if (hipMemcpy(d, rows.data(), row_bytes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy((char*)d + row_bytes, lut.data(), lut_bytes, hipMemcpyHostToDevice) !=
-          hipSuccess) {
+          hipSuccess ||
+      (map256 && hipMemcpy((char*)d + row_bytes + lut_bytes, map256, map_bytes,
+                           hipMemcpyHostToDevice) != hipSuccess)) {
     (void)hipFree(d);
     return RC_E_DEVICE;
   }
   rc_model* mm = new rc_model;
   memset(mm, 0, sizeof *mm);
-  mm->kind = RC_KIND_SET;
+  mm->kind = kind;
   mm->device = ctx->device;
   mm->div = (total_freq & (total_freq - 1)) == 0 ? DIV_POW2 : DIV_MAGIC;
   mm->dmem = d;
   mm->plan = plan;
-  SetArgs& a = mm->set;
+  SetArgs& a = kind == RC_KIND_ORDER1 ? mm->o1.s : mm->set;
   a.m.n = n_symbols;
   a.m.ftotal = (float)total_freq;
   div_constants(a.m, total_freq);
@@ -705,8 +716,25 @@ rc_status rc_model_create_static_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_
   a.lut = (const u32*)((char*)d + row_bytes);
   a.k = n_models;
   a.tab_bytes = plan.enc_tab;
+  if (kind == RC_KIND_ORDER1) {
+    mm->o1.map = (const uint8_t*)d + row_bytes + lut_bytes;
+    mm->o1.first_row = first_row;
+  }
   *out = mm;
   return RC_OK;
+}
+
+rc_status rc_model_create_static_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                     const uint32_t* c_freq, const uint32_t* cum_freq,
+                                     uint32_t total_freq, rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
+  *out = nullptr;
+  const rc_status ok = set_check(n_models, n_symbols, c_freq, cum_freq, total_freq);
+  if (ok != RC_OK) return ok;
+  SetPlan plan;
+  rc_set_plan(n_models, total_freq, &plan);
+  return set_build(ctx, RC_KIND_SET, n_models, n_symbols, c_freq, cum_freq, total_freq, plan,
+                   nullptr, 0, out);
 }
 
 rc_status rc_encode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_t* syms,
@@ -743,6 +771,94 @@ rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_
       rc_set_decode_launch(ctx->cur, ctx->knobs, set->set, set->div, set->plan, code, code_off,
                            code_len, idx, syms_out, sym_off, n_chunks, flags);
   return e == hipSuccess ? RC_OK : device_error(e, "indexed decode launch");
+}
+
+// ---- order-1 sets (rc_order1.h; kernels in rc_order1.hip) ----
+
+// what rc_model_create_order1_set accepts beyond the set's rules (include/range_coder.h)
+static rc_status order1_check(u32 n_models, u32 n_symbols, const u32* c, const u32* cum,
+                              u32 total, const uint8_t* ctx_map, u32 first_row) {
+  if (!ctx_map) return RC_E_ARG;
+  const rc_status ok = set_check(n_models, n_symbols, c, cum, total);
+  if (ok != RC_OK) return ok;
+  if (first_row >= n_models) return RC_E_BAD_MODEL;
+  for (u32 s = 0; s < n_symbols; ++s)
+    if (ctx_map[s] >= n_models) return RC_E_BAD_MODEL;
+  return RC_OK;
+}
+
+// Internal test hooks (not in include/range_coder.h; host only, no device needed).
+// rc_model_order1_check_: rc_model_create_order1_set's validation of its tables and its map.
+rc_status rc_model_order1_check_(uint32_t n_models, uint32_t n_symbols, const uint32_t* c_freq,
+                                 const uint32_t* cum_freq, uint32_t total_freq,
+                                 const uint8_t* ctx_map, uint32_t first_row) {
+  return order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, ctx_map, first_row);
+}
+// rc_model_order1_plan_: rc_model_set_plan_ for an order-1 set (the decoder's LDS includes the
+// map; the encoder's numbers are the set's).
+rc_status rc_model_order1_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* out) {
+  if (!out) return RC_E_ARG;
+  if (n_models < 1 || n_models > RC_MAX_SET_MODELS || total_freq < 256 || total_freq > 65536)
+    return RC_E_BAD_MODEL;
+  SetPlan p;
+  rc_order1_plan(n_models, total_freq, &p);
+  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
+                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
+  memcpy(out, v, sizeof v);
+  return RC_OK;
+}
+
+rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                     const uint32_t* c_freq, const uint32_t* cum_freq,
+                                     uint32_t total_freq, const uint8_t* ctx_map,
+                                     uint32_t first_row, rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !ctx_map || !out) return RC_E_ARG;
+  *out = nullptr;
+  const rc_status ok =
+      order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, ctx_map, first_row);
+  if (ok != RC_OK) return ok;
+  SetPlan plan;
+  rc_order1_plan(n_models, total_freq, &plan);
+  // the kernels stage 256 entries: a symbol past the alphabet (a flagged chunk) maps to row 0
+  uint8_t map256[256] = {0};
+  memcpy(map256, ctx_map, n_symbols);
+  return set_build(ctx, RC_KIND_ORDER1, n_models, n_symbols, c_freq, cum_freq, total_freq, plan,
+                   map256, first_row, out);
+}
+
+rc_status rc_encode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,
+                                 const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
+                                 const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
+  if (!ctx || !o1 || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (o1->kind != RC_KIND_ORDER1) return RC_E_ARG;  // kinds do not mix
+  if (n_chunks == 0) return RC_OK;
+  if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
+  if (o1->device != ctx->device) return RC_E_ARG;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  rc_svc_yield_all_();
+  const hipError_t e =
+      rc_order1_encode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div, o1->plan, syms, sym_off,
+                              n_chunks, out, out_off, out_len, flags);
+  return e == hipSuccess ? RC_OK : device_error(e, "order-1 encode launch");
+}
+
+rc_status rc_decode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* code,
+                                 const uint64_t* code_off, const uint64_t* code_len,
+                                 uint8_t* syms_out, const uint64_t* sym_off, uint32_t n_chunks,
+                                 uint32_t* flags) {
+  if (!ctx || !o1 || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (o1->kind != RC_KIND_ORDER1) return RC_E_ARG;  // kinds do not mix
+  if (n_chunks == 0) return RC_OK;
+  if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
+  if (o1->device != ctx->device) return RC_E_ARG;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  rc_svc_yield_all_();
+  const hipError_t e =
+      rc_order1_decode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div, o1->plan, code, code_off,
+                              code_len, syms_out, sym_off, n_chunks, flags);
+  return e == hipSuccess ? RC_OK : device_error(e, "order-1 decode launch");
 }
 
 // rc_encode_host / rc_decode_host: the pipelined host path lives in rc_stream.hip

@@ -155,6 +155,78 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   if (hist && acc) atomicAdd(reinterpret_cast<unsigned long long*>(hist + tid), (unsigned long long)acc);
 }
 
+// k_histogram_order1: pair counts by context class, the counts an order-1 set's rows are
+// quantised from (rc_order1.h).  Row j of the result counts the symbols whose context row is j:
+// first_row for a chunk's first symbol, map[previous symbol] for every other one.  Chunk-stride
+// workgroups; a thread takes 16 consecutive symbols and the one before them; K x 256 u32 counters
+// in LDS (dynamic, at most 64 KiB) and the 256-B map behind them, flushed into the u64 result
+// before a counter can wrap: at most 2^32 - 1 symbols are counted between two flushes, so no
+// counter exceeds that whatever the data.
+struct O1HistMap {
+  u32 w[64];  // the 256 map bytes
+};
+typedef u32x4 u32x4_h1 __attribute__((aligned(1)));
+#define O1H_SEG (1ull << 30)  // symbols of a chunk counted between two looks at the budget
+
+__global__ __launch_bounds__(256) void k_histogram_order1(
+    O1HistMap map, u32 first_row, u32 K, const uint8_t* __restrict__ syms,
+    const u64* __restrict__ sym_off, u32 n_chunks, u64* __restrict__ hist) {
+  extern __shared__ u32 s_h1[];
+  const u32 tid = threadIdx.x;
+  const uint8_t* const s_map = reinterpret_cast<const uint8_t*>(s_h1 + K * 256u);
+  for (u32 j = tid; j < K * 256u; j += 256) s_h1[j] = 0;
+  if (tid < 64) s_h1[K * 256u + tid] = map.w[tid];
+  __syncthreads();
+  auto flush = [&]() {
+    __syncthreads();
+    for (u32 j = 0; j < K; ++j) {
+      const u32 v = s_h1[j * 256u + tid];
+      if (v) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(hist + j * 256u + tid),
+                  (unsigned long long)v);
+        s_h1[j * 256u + tid] = 0;
+      }
+    }
+    __syncthreads();
+  };
+  u64 pending = 0;  // symbols counted since the last flush (workgroup-uniform)
+  for (u32 k = blockIdx.x; k < n_chunks; k += gridDim.x) {
+    const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
+    const uint8_t* p = syms + s0;
+    for (u64 b0 = 0; b0 < n; b0 += O1H_SEG) {
+      const u64 b1 = n - b0 < O1H_SEG ? n : b0 + O1H_SEG;
+      if (pending + (b1 - b0) > 0xFFFFFFFFull) {
+        flush();
+        pending = 0;
+      }
+      pending += b1 - b0;
+      for (u64 i = b0 + 16ull * tid; i < b1; i += 16ull * 256) {
+        u32 row = i ? (u32)s_map[p[i - 1]] : first_row;  // chunk boundaries reset the context
+        if (i + 16 <= b1) {
+          const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
+          const u32 ws[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const u32 s = (ws[q] >> (8 * j)) & 255u;
+              atomicAdd(&s_h1[row * 256u + s], 1u);
+              row = s_map[s];
+            }
+          }
+        } else {
+          for (u64 j = i; j < b1; ++j) {
+            const u32 s = p[j];
+            atomicAdd(&s_h1[row * 256u + s], 1u);
+            row = s_map[s];
+          }
+        }
+      }
+    }
+  }
+  flush();
+}
+
 // per chunk: bits = sum_i hist[i] * icl[i] in f64 (icl[i] = +inf for c_i == 0: the reference's
 // ideal_code_length returns Err there, pmodel.rs:16-18).  One wave per chunk: lane L reads bins
 // 4L .. 4L+3 of the row as one 16-B load (the wave reads the whole 1-KiB row at once) and holds
@@ -190,6 +262,7 @@ __global__ __launch_bounds__(HWG) void k_ideal_bits(const double* __restrict__ i
 // Host side
 // ------------------------------------------------------------------------------------------
 struct rc_ctx;  // rc_kernels.hip
+hipError_t set_allow_lds(const void* kernel);  // rc_indexed.hip: a whole CU's LDS as dynamic LDS
 extern "C" {
 rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device);  // rc_kernels.hip
 }
@@ -228,6 +301,37 @@ rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms, const uint64_t* sym_off
   // off (measurements)
   hipLaunchKernelGGL(k_histogram, dim3(grid), dim3(256), 0, s, syms, sym_off, n_chunks,
                      chunk_hist, hist, (u32)rc_ctx_knobs_(ctx).hist_hot);
+  return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+}
+
+rc_status rc_histogram_order1(rc_ctx* ctx, uint32_t n_models, const uint8_t* ctx_map_host,
+                              uint32_t first_row, const uint8_t* syms, const uint64_t* sym_off,
+                              uint32_t n_chunks, uint64_t* hist) {
+  hipStream_t s;
+  int dev;
+  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS || !ctx_map_host ||
+      n_models < 1 || n_models > RC_MAX_SET_MODELS || first_row >= n_models)
+    return RC_E_ARG;
+  O1HistMap map;
+  for (u32 i = 0; i < 256; ++i)
+    if (ctx_map_host[i] >= n_models) return RC_E_ARG;
+  memcpy(map.w, ctx_map_host, 256);
+  if (n_chunks == 0) return RC_OK;
+  if (!syms || !sym_off || !hist) return RC_E_ARG;
+  DevSet g(dev);
+  rc_svc_yield_all_();
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return RC_E_DEVICE;
+  // K KiB of counters and the map per workgroup (just over the default 64-KiB limit of dynamic
+  // LDS at K = 64); up to 8 workgroups (32 waves) per CU
+  const u32 lds = n_models * 1024u + 256u;
+  if (set_allow_lds(reinterpret_cast<const void*>(k_histogram_order1)) != hipSuccess)
+    return RC_E_DEVICE;
+  const u32 per_cu = std::max(1u, std::min(8u, 163840u / lds));
+  const u32 grid = std::min<u32>(n_chunks, (u32)cus * per_cu);
+  hipLaunchKernelGGL(k_histogram_order1, dim3(grid), dim3(256), lds, s, map, first_row, n_models,
+                     syms, sym_off, n_chunks, hist);
   return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
 }
 

@@ -1,0 +1,35 @@
+// rc_order1.h — order-1 sets (rc_model_create_order1_set): the K rows of a static model set
+// (rc_indexed.h) plus a context map, and batch coders in which the previous symbol of the chunk
+// picks the row: row_0 = first_row, row_i = ctx_map[sym[i-1]] (rc_encode_batch_order1 /
+// rc_decode_batch_order1; kernels in rc_order1.hip).
+//
+// Everything the set's kernels rely on holds unchanged (one total, at most 3 bytes settled per
+// symbol, one workgroup per CU staging the rows once).  What is new is the map in LDS, staged as
+// premultiplied LDS offsets so that the row of the next symbol costs one dependent LDS read:
+//   encoder: 256 x u32, the byte offset of the row (in the place of the indexed encoder's poison
+//            row K, which an order-1 set cannot reach: the map is validated at creation), so the
+//            encoder's LDS plan is the set's;
+//   decoder: 256 x u32 behind the rows, (row byte address >> 2) | (bucket base in words << 16),
+//            1 KiB more than the set's plan, counted by rc_order1_plan.
+#pragma once
+#include "rc_indexed.h"
+
+#define O1_MAP_BYTES 1024u  // 256 premultiplied u32 entries
+
+// The set's plan with the decoder's map counted in (enc_*: exactly rc_set_plan's)
+void rc_order1_plan(u32 n_models, u32 total, SetPlan* p);
+
+struct O1Args {
+  SetArgs s;           // the rows and buckets, built for rc_order1_plan's dec_bits
+  const uint8_t* map;  // [256] rows (device): ctx_map, entries from n_symbols on = 0
+  u32 first_row;       // the row of every chunk's first symbol
+};
+
+hipError_t rc_order1_encode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a, int div,
+                                   const SetPlan& p, const uint8_t* syms, const u64* sym_off,
+                                   u32 n_chunks, uint8_t* out, const u64* out_off, u64* out_len,
+                                   u32* flags);
+hipError_t rc_order1_decode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a, int div,
+                                   const SetPlan& p, const uint8_t* code, const u64* code_off,
+                                   const u64* code_len, uint8_t* syms_out, const u64* sym_off,
+                                   u32 n_chunks, u32* flags);

@@ -1,0 +1,592 @@
+// rc_order1.hip — k_encode_order1 / k_decode_order1: the indexed coders (rc_indexed.hip) with the
+// row of each symbol chosen by the chunk's previous symbol through a context map (order-1 sets,
+// rc_order1.h).  Symbol i of a chunk is coded exactly as encoder.encode(&models[row_i], sym[i]) /
+// decoder.decode(&models[row_i]), row_0 = first_row, row_i = ctx_map[sym[i-1]].  The arithmetic,
+// both rings, the flush rounds, dec_apply and dec_rare are those of the single-table coders
+// (rc_encode.inc, rc_decode.inc, rc_static.h); the rows, buckets and the launch shape are the
+// set's.  There is no index stream: the encoder takes the previous symbol from its tile, the
+// decoder carries the row from one decoded symbol to the next in a register.
+#define RC_DEC_SHARED_ONLY
+#include "rc_order1.h"
+
+#include "rc_encode.inc"
+#include "rc_decode.inc"
+
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+
+// dummy symbol tiles of dead lanes (zeros)
+__device__ uint4 g_o1sink[4];
+
+// ------------------------------------------------------------------------------------------
+// Encoder
+// ------------------------------------------------------------------------------------------
+
+// bytes of one staged row: 256 8-B (cum, c) entries (layout 0) or cum[0 .. 256] (layout 1)
+template <int LAYOUT>
+static __device__ __forceinline__ u32 o1_row_bytes() {
+  return LAYOUT == 0 ? 2048u : 4u * SET_ROW_WORDS;
+}
+
+// the (cum, c) entry of symbol s in the row at LDS byte offset ro, in enc_core's SM 1 form (as
+// set_entry of rc_indexed.hip, without the clamp to a poison row: ro comes from the staged map)
+template <int LAYOUT>
+static __device__ __forceinline__ uint2 o1_row_entry(u32 ro, u32 s) {
+  if (LAYOUT == 0) {
+    const u32x2 v = *(const __attribute__((address_space(3))) u32x2*)(uintptr_t)(ro + (s << 3));
+    return make_uint2(v.x, v.y);
+  }
+  const l_u32* rp = (const l_u32*)(uintptr_t)(ro + (s << 2));
+  const u32 c0 = rp[0], c1 = rp[1];
+  const u32 c = c1 - c0;
+  return make_uint2(c0 | ((c - 1u) & 0xFF000000u), max(c, 1u));
+}
+
+// the row offset the map gives for previous symbol p (a byte: every one of the 256 staged
+// entries is a row of the set, so a symbol past the alphabet reads a harmless row too)
+static __device__ __forceinline__ u32 o1_map(u32 map_off, u32 p) {
+  return *(const l_u32*)(uintptr_t)(map_off + (p << 2));
+}
+
+// 16 symbols (one 16-B load), as set_enc16: the table entry is read two symbols ahead, pairs
+// share one rare test, a flush check after every 8 symbols.  ro: the row of the tile's first
+// symbol, carried from the symbol before the tile; the other 15 rows come from the tile itself
+// (the row of symbol j is map[symbol j - 1]).  Leaves the row of the next tile's first symbol in
+// ro.
+template <int DIV, int LAYOUT>
+static __device__ __forceinline__ void o1_enc16(Enc& e, const ModelArgs& m, u32 map_off, uint4 v,
+                                                u32& ro, bool act, u32 lane, const u32* wring,
+                                                const EncOut* wout, u32* wrank) {
+  const u32 ws[4] = {v.x, v.y, v.z, v.w};
+#define O1_SYM(j) ((ws[(j) >> 2] >> (8 * ((j) & 3))) & 255u)
+  // the rows of all 16 symbols (and of the next block's first) are read before the block is
+  // coded: they depend on the tile alone, and issued here they are not held back behind the
+  // coder's ring stores, which the compiler must assume to alias the map
+  u32 r[17];
+  r[0] = ro;
+#pragma unroll
+  for (int j = 1; j <= 16; ++j) r[j] = o1_map(map_off, O1_SYM(j - 1));
+  uint2 t = o1_row_entry<LAYOUT>(r[0], O1_SYM(0));
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int i = 0; i < 4; i += 2) {
+      const int j = 4 * q + i;
+      const uint2 t1 = o1_row_entry<LAYOUT>(r[j + 1], O1_SYM(j + 1));
+      // (past the tile's end: a harmless read of the last symbol in the next row)
+      const uint2 tn = o1_row_entry<LAYOUT>(r[j + 2], O1_SYM(j + 2 < 16 ? j + 2 : 15));
+      enc_sym2<DIV, 1>(e, m, t, t1, act, lane, wring, wout, wrank);
+      t = tn;
+    }
+    if (q & 1) enc_flush(e, lane, wring, wout, wrank);
+  }
+#undef O1_SYM
+  if (act) ro = r[16];
+}
+
+// one symbol fetched byte-wise (unaligned head / tail of a chunk)
+template <int DIV, int LAYOUT>
+static __device__ __forceinline__ void o1_enc_byte(Enc& e, const ModelArgs& m, u32 map_off,
+                                                   const uint8_t* sp, u64 i, u32& ro, bool act,
+                                                   u32 lane, const u32* wring, const EncOut* wout,
+                                                   u32* wrank) {
+  const u32 sym = act ? (u32)sp[i] : 0u;
+  enc_sym<DIV, 1>(e, m, o1_row_entry<LAYOUT>(ro, sym), act, lane, wring, wout, wrank);
+  const u32 rn = o1_map(map_off, sym);
+  if (act) ro = rn;
+}
+
+// the first symbol of a chunk the reference cannot encode (rare: flagged chunks only), walked
+// with the context as the reference's caller would
+static __device__ u32 o1_first_error(const u32* rows, const uint8_t* map, u32 first_row,
+                                     u32 n_symbols, const uint8_t* sp, u64 n) {
+  u32 j = first_row;
+  for (u64 i = 0; i < n; ++i) {
+    const u32 s = sp[i];
+    if (s >= n_symbols) return RC_F_BAD_SYMBOL;
+    const u32* row = rows + j * SET_ROW_WORDS;
+    if (row[s + 1] == row[s]) return RC_F_ZERO_FREQ;
+    j = map[s];
+  }
+  return 0;
+}
+
+template <int DIV, int LAYOUT>
+__global__ __launch_bounds__(1024) void k_encode_order1(
+    O1Args oa, const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
+    uint8_t* __restrict__ out, const u64* __restrict__ out_off, u64* __restrict__ out_len,
+    u32* __restrict__ flags) {
+  const SetArgs& a = oa.s;
+  rc_set_prio(a.m);
+  // dynamic LDS, sized by the plan: the K rows at address 0, the map in the place of the indexed
+  // encoder's row K, then (1-KiB aligned) 8 KiB of rings per wave, the lanes' output geometry
+  // and the waves' rank tables
+  extern __shared__ __attribute__((aligned(1024))) u32 s_enc[];
+  const u32 tid = threadIdx.x, lanes = blockDim.x, K = a.k;
+  const ModelArgs& m = a.m;
+  const u32 map_off = K * o1_row_bytes<LAYOUT>();
+  if (LAYOUT == 0) {
+    for (u32 en = tid; en < K * 256u; en += lanes) {
+      const u32 row = en >> 8, s = en & 255u;
+      const u32 c0 = a.rows[row * SET_ROW_WORDS + s], c1 = a.rows[row * SET_ROW_WORDS + s + 1];
+      const uint2 t = s >= m.n ? make_uint2(RC_F_BAD_SYMBOL << 24, 1u)
+                      : c1 == c0 ? make_uint2(RC_F_ZERO_FREQ << 24, 1u) : make_uint2(c0, c1 - c0);
+      s_enc[2 * en] = t.x;
+      s_enc[2 * en + 1] = t.y;
+    }
+  } else {
+    for (u32 en = tid; en < K * SET_ROW_WORDS; en += lanes) s_enc[en] = a.rows[en];
+  }
+  for (u32 p = tid; p < 256u; p += lanes)
+    s_enc[map_off / 4 + p] = (u32)oa.map[p] * o1_row_bytes<LAYOUT>();
+  const u32 nw = lanes >> 6;
+  u32* const s_ring = s_enc + a.tab_bytes / 4;
+  EncOut* const s_out = reinterpret_cast<EncOut*>(s_ring + nw * ENC_RING * 64);
+  u32* const s_rank = reinterpret_cast<u32*>(s_out + lanes);
+  const u32 lane = tid & 63, wave = tid >> 6;
+  const u32 k = blockIdx.x * lanes + tid;
+  const bool live = k < n_chunks;  // dead lanes still take part in the wave's flush rounds
+  RC_VGPR_FLOOR_128();
+
+  u64 s0 = 0, n = 0, o0 = 0, o1 = 0;
+  if (live) {
+    s0 = sym_off[k];
+    n = sym_off[k + 1] - s0;
+    o0 = out_off[k];
+    o1 = out_off[k + 1];
+  }
+  // B (bit position) is 32-bit: a longer chunk is flagged, not read, and its slot not written
+  const bool too_long = n > RC_MAX_CHUNK_SYMBOLS;
+  if (too_long) {
+    n = 0;
+    o1 = o0;
+  }
+  const u32 al = (u32)(((uintptr_t)out + o0) & (ENC_UNIT - 1));
+  u64 cap = o1 - o0;
+  if (cap > 0xFFFFFF00ull - al) cap = 0xFFFFFF00ull - al;
+  s_out[tid].gbase = out + o0 - al;
+  s_out[tid].lo_ok = al;
+  s_out[tid].hi_ok = al + (u32)cap;
+  __syncthreads();
+  const u32* wring = s_ring + wave * ENC_RING * 64;
+  const EncOut* wout = s_out + wave * 64;
+  u32* const wrank = s_rank + wave * 64;
+
+  Enc e;
+  e.low = 0;  // RangeCoder::default (range_coder.rs:13-20)
+  e.range = ~0ull;
+  e.acc = 0;
+  e.B = 8 * al;  // pad bytes in front of the slot (never stored)
+  e.fthr = 8u * FLUSH_AT;  // fpos = 0
+  e.err = 0;
+  e.ring = a.tab_bytes + 4u * (wave * ENC_RING * 64 + ring_col(lane));
+
+  const uint8_t* sp = syms + s0;
+  u32 ro = oa.first_row * o1_row_bytes<LAYOUT>();  // the row of the lane's next symbol
+  // (n <= 2^25 here: the symbol counters are 32-bit, which keeps the tile registers free)
+  const u32 nn = (u32)n;
+  u32 head = (64 - ((u32)(uintptr_t)sp & 63)) & 63;  // symbols before the first 64-B aligned tile
+  if (head > nn) head = nn;
+  const u32 ntile = (nn - head) >> 6;
+  // head: byte-wise, all lanes in step (flush rounds are wave-wide)
+  for (u32 i = 0; __any((int)(i < head)); ++i) {
+    o1_enc_byte<DIV, LAYOUT>(e, m, map_off, sp, i, ro, i < head, lane, wring, wout, wrank);
+    if ((i & 7) == 7) enc_flush(e, lane, wring, wout, wrank);
+  }
+  // body, part 1: the tiles every live lane of the wave has, with every lane active; dead lanes
+  // run along on a dummy tile and a slot with no writable bytes
+  u32 tm = live ? ntile : ~0u;
+#pragma unroll
+  for (int o = 32; o; o >>= 1) tm = min(tm, (u32)__shfl_xor((int)tm, o));
+  if (tm == ~0u) tm = 0;  // no live lane in this wave
+  const u32 tmin = __builtin_amdgcn_readfirstlane(tm);  // wave-uniform (scalar) trip count
+  const uint8_t* tp = live ? sp + head : reinterpret_cast<const uint8_t*>(g_o1sink);
+  // 64-symbol tiles, 4 x 16 B per lane, the next tile in flight while the current one is coded
+  // (explicit registers, as in k_encode_static)
+  const u32 tstep = live ? 64 : 0;  // bytes per tile
+  uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0, c2 = c0, c3 = c0;
+  if (tmin) {
+    const uint4* q = reinterpret_cast<const uint4*>(tp);
+    c0 = q[0];
+    c1 = q[1];
+    c2 = q[2];
+    c3 = q[3];
+  }
+  for (u32 t = 0; t < tmin; ++t) {
+    rc_prio_rotate(m.prio_rot);
+    uint4 n0 = c0, n1 = c1, n2 = c2, n3 = c3;
+    if (t + 1 < tmin) {
+      const uint4* q = reinterpret_cast<const uint4*>(tp + (u64)(t + 1) * tstep);
+      n0 = q[0];
+      n1 = q[1];
+      n2 = q[2];
+      n3 = q[3];
+    }
+    o1_enc16<DIV, LAYOUT>(e, m, map_off, c0, ro, true, lane, wring, wout, wrank);
+    o1_enc16<DIV, LAYOUT>(e, m, map_off, c1, ro, true, lane, wring, wout, wrank);
+    o1_enc16<DIV, LAYOUT>(e, m, map_off, c2, ro, true, lane, wring, wout, wrank);
+    o1_enc16<DIV, LAYOUT>(e, m, map_off, c3, ro, true, lane, wring, wout, wrank);
+    c0 = n0;
+    c1 = n1;
+    c2 = n2;
+    c3 = n3;
+  }
+  // body, part 2 (ragged waves): the remaining 16-symbol blocks of the tiles, lanes masked (a
+  // masked lane keeps its carried row)
+  const u32 nblk = ntile * 4;
+  for (u32 b = tmin * 4; __any((int)(b < nblk)); ++b) {
+    const bool act = b < nblk;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (act) v = reinterpret_cast<const uint4*>(tp)[b];
+    o1_enc16<DIV, LAYOUT>(e, m, map_off, v, ro, act, lane, wring, wout, wrank);
+  }
+  const u32 tail0 = head + (ntile << 6);
+  for (u32 j = 0; __any((int)(tail0 + j < nn)); ++j) {  // j is wave-uniform
+    o1_enc_byte<DIV, LAYOUT>(e, m, map_off, sp, tail0 + j, ro, tail0 + j < nn, lane, wring, wout,
+                             wrank);
+    if ((j & 7) == 7) enc_flush(e, lane, wring, wout, wrank);
+  }
+
+  // Encoder::finish (encoder.rs:40-46): 8 x left_shift
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    enc_emit_byte(e, (u32)(e.low >> 56));
+    e.low <<= 8;
+  }
+  const u32 len = (e.B >> 3) - al;
+  u32 wend = enc_wpos(e);
+  if (e.B & 31) {  // the last, incomplete dword
+    ring_put(e.ring, (e.B >> 5) & (ENC_RING - 1), (u32)(e.acc << (32 - (e.B & 31))));
+    wend += 4;
+  }
+  // final rounds: the last (partial) units, clipped to the stream end
+  const u32 end = al + len;
+  if (end < s_out[tid].hi_ok) s_out[tid].hi_ok = end;
+  while (__any((int)(enc_fpos(e) < wend)))
+    enc_round(e, enc_fpos(e) < wend, lane, wring, wout, wrank);
+  if (live) {
+    e.err = (e.err >> 24) ? o1_first_error(a.rows, oa.map, oa.first_row, m.n, sp, n) : 0u;
+    if (!e.err && (u64)len > cap) e.err = RC_F_CAPACITY;
+    out_len[k] = too_long ? 0u : len;
+    flags[k] = too_long ? RC_F_TOO_LONG : e.err;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Decoder
+// ------------------------------------------------------------------------------------------
+typedef Dec<DEC_LD, 0> O1Dec;
+
+// (cum, c) of symbol s from the cum-only row at LDS byte address rowa (set_row_entry and
+// set_dec_fix are file-local to rc_indexed.hip; restated here, as §9.5 restated dec_fix, so that
+// no existing kernel's code depends on this file)
+static __device__ __forceinline__ uint2 o1_cum_entry(u32 rowa, u32 s) {
+  const l_u32* rp = (const l_u32*)(uintptr_t)(rowa + (s << 2));
+  const u32 c0 = rp[0], c1 = rp[1];
+  return make_uint2(c0, c1 - c0);
+}
+
+// the exact index s = #{ j in [1, n-1] : r * cum[j] <= x } (FreqTable::find_index) over a
+// cum-only row, walked from the candidate
+static __device__ __forceinline__ void o1_dec_fix(u32& s, uint2& t, u64& A, u64& B, u64 x, u64 r,
+                                                  u32 rowa, u32 n) {
+  s &= 255u;
+  if (A > x) {
+    do {
+      --s;
+      t = o1_cum_entry(rowa, s);
+      A = r * (u64)t.x;
+    } while (A > x);
+    B = r * (u64)t.y;
+  } else {
+    while (s + 1 < n && x - A >= B) {
+      ++s;
+      t = o1_cum_entry(rowa, s);
+      A = r * (u64)t.x;
+      B = r * (u64)t.y;
+    }
+  }
+}
+
+// the decoder's map word of row j: (LDS byte address of the cum row >> 2) | (the row's first
+// bucket, in words) << 16; both are below 40,960 (160 KiB of 4-B words)
+static __device__ __forceinline__ u32 o1_ctx_word(u32 j, u32 rows_off, u32 lut_bits) {
+  return ((rows_off + j * (4u * SET_ROW_WORDS)) >> 2) | ((j << lut_bits) << 16);
+}
+
+// Decoder::decode(&models[row]) with FreqTable::find_index over that row, as set_dec_sym
+// (rc_indexed.hip).  cw is the carried context: the map word of the row of THIS symbol.  The word
+// of the next symbol's row, map[s], is read beside the candidate's (cum, c) and read again after
+// a fix-up moved s, so cw is replaced only once the exact verification has fixed the symbol, and
+// the next symbol's bucket read waits for one LDS read, not for a row number to be scaled.
+template <int DIV>
+static __device__ __forceinline__ u32 o1_dec_sym(O1Dec& d, const ModelArgs& m, u32 map_off,
+                                                 u32& cw) {
+  u32 roff, raddr;
+  asm("v_and_b32 %0, %1, %2" : "=v"(roff) : "i"((DEC_RING - 1) << 5), "v"(d.bpos));
+  asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(raddr) : "v"(roff), "v"((u32)(uintptr_t)d.ring));
+  const l_u32* rp = (const l_u32*)(uintptr_t)raddr;
+  const u32 D0 = rp[0], D1 = rp[O1Dec::kS];
+  const u64 r = range_par_total<DIV, 1>(d.range, m);
+  const float X = (float)(d.dhi() - hi32(d.low));
+  const u32 qh = hint_floor(X, d.G);
+  // the row's bucket (buckets at LDS address 0, 2^lut_bits 4-B entries per row)
+  const u32 la = ((cw >> 16) + __builtin_amdgcn_ubfe(qh, m.lut_shift, m.lut_bits)) << 2;
+  const u32 ent = *(const l_u32*)(uintptr_t)la;
+  const u32 below = smask((qh & 0xFFFFu) - (ent >> 16));
+  u32 s = __builtin_amdgcn_ubfe(ent, mselc(below, 0u, 8u), 8);
+  const u32 rowa = (cw & 0xFFFFu) << 2;
+  uint2 t = o1_cum_entry(rowa, s);
+  u32 nw = *(const l_u32*)(uintptr_t)(map_off + (s << 2));  // (s < 256: inside the staged map)
+  float tc = m.ftotal * __builtin_amdgcn_rcpf(cvt_f32(t.y));  // (hint only)
+  u64 B = mul_rv<1>(r, t.y);
+  u64 A = mul_rv<1>(r, t.x);
+  const u64 dx = sub64((u32)d.dat, d.dhi(), d.low + A);  // x - r cum
+  if (__builtin_expect(__any((int)(dx >= B)), 0)) {
+    if (dx >= B) {
+      o1_dec_fix(s, t, A, B, d.x(), r, rowa, m.n);
+      nw = *(const l_u32*)(uintptr_t)(map_off + (s << 2));
+      tc = m.ftotal * __builtin_amdgcn_rcpf(cvt_f32(t.y));
+      // the buckets only hold symbols with c > 0, so c == 0 can only come from the fix-up: corrupt
+      // input (the reference loops forever); an over-read, if any, came first
+      if (t.y == 0) {
+        d.err = d.err ? d.err : (d.bpos > d.limb ? RC_F_TRUNCATED : RC_F_CORRUPT);
+        B = r;
+      }
+    }
+  }
+  dec_apply<1, 4>(d, d.low + A, B, d.dat, tc, D0, D1, 0u);
+  const bool rare = hi32(d.range) < 0x10000u;  // range_reduction_expansion
+  if (__builtin_expect(__any((int)rare), 0)) {
+    if (rare) {
+      dec_rare(d, DEC_NEED_SM);
+      dec_gexact<1, 4>(d, m);
+    }
+  }
+  cw = nw;
+  return s;
+}
+
+// 16 symbols into one 16-B block, with the ring checks
+template <int DIV>
+static __device__ __forceinline__ uint4 o1_phase16(O1Dec& d, const ModelArgs& m, u32 map_off,
+                                                   u32& cw) {
+  dec_gexact<1, 4>(d, m);  // bounds the drift of the carried scale to 16 symbols
+  u32 w[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) w[q] = put_byte(w[q], o1_dec_sym<DIV>(d, m, map_off, cw), jj);
+    if (q < 3 && ((q + 1) * 4) % DEC_CHECK_SPAN == 0) dec_check4<1, DEC_NEED_SPAN>(d);
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+template <int DIV>
+__global__ __launch_bounds__(1024) void k_decode_order1(
+    O1Args oa, const uint8_t* __restrict__ code, const u64* __restrict__ code_off,
+    const u64* __restrict__ code_len, uint8_t* __restrict__ syms_out,
+    const u64* __restrict__ sym_off, u32 n_chunks, u32* __restrict__ flags) {
+  const SetArgs& a = oa.s;
+  rc_set_prio(a.m);
+  // dynamic LDS, sized by the plan: the K rows' buckets at address 0 (a bucket read needs no
+  // base add), the K cum-only rows, the map, then the code rings
+  extern __shared__ u32 s_dyn[];
+  const u32 tid = threadIdx.x, lanes = blockDim.x, K = a.k;
+  const ModelArgs& m = a.m;
+  const u32 lut_words = K << m.lut_bits;
+  const u32 rows_off = 4u * lut_words;
+  const u32 map_off = rows_off + 4u * K * SET_ROW_WORDS;
+  for (u32 j = tid; j < lut_words; j += lanes) s_dyn[j] = a.lut[j];
+  for (u32 j = tid; j < K * SET_ROW_WORDS; j += lanes) s_dyn[lut_words + j] = a.rows[j];
+  for (u32 p = tid; p < 256u; p += lanes)
+    s_dyn[map_off / 4 + p] = o1_ctx_word(oa.map[p], rows_off, m.lut_bits);
+  __syncthreads();
+  const u32 k = blockIdx.x * lanes + tid;
+  if (k >= n_chunks) return;
+  // f32 rounding toward zero from here on (MODE.FP_ROUND f32 bits = 3), for hint_floor
+  asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 3");
+  RC_VGPR_FLOOR_128();
+  const u32 lane = tid & 63, wave = tid >> 6;
+
+  const u64 c0 = code_off[k];
+  const u64 clen = code_len[k];
+  const u64 s0 = sym_off[k];
+  const u64 n64 = sym_off[k + 1] - s0;
+  uint8_t* op = syms_out + s0;
+  if (n64 > RC_MAX_CHUNK_SYMBOLS) {  // 32-bit stream positions (include/range_coder.h)
+    flags[k] = RC_F_TOO_LONG;
+    return;
+  }
+  if (clen < 8) {  // Decoder::new panics (decoder.rs:21, :33)
+    flags[k] = RC_F_TRUNCATED;
+    return;
+  }
+  const u32 n = (u32)n64;  // (<= 2^25: the counters below are 32-bit)
+  const uint8_t* cp = code + c0;
+  constexpr u32 GAL = 16 * DEC_LD;  // load bursts are whole aligned 64-B segments
+  const u32 al = (u32)((uintptr_t)cp & (GAL - 1));
+
+  O1Dec d;
+  d.low = 0;
+  d.range = ~0ull;
+  d.err = 0;
+  d.fillb = 0;
+  d.pend_ok = 0;
+  d.ring = (l_u32*)(uintptr_t)(map_off + O1_MAP_BYTES) + wave * DEC_RING_ALLOC * 64 + lane;
+  d.gbase = reinterpret_cast<const uint4*>(cp - al);
+  d.gnext = 0;
+  // n <= 2^25 symbols consume at most 8 + 12 n < 2^29 bytes: code past 2^29 is never read
+  const u32 lim = (u32)(clen < (1ull << 29) - al ? al + clen : 1ull << 29);
+  d.glast = ((lim - 1) >> 4) & ~(u32)(DEC_LD - 1);  // (the last segment's first block)
+  d.bpos = 8 * (al + 8);  // Decoder::new primes 8 bytes (decoder.rs:21)
+  d.limb = 8 * lim;
+  // fill the whole ring, and have the next load burst in flight (as k_decode_static)
+#pragma unroll
+  for (int h = 0; h < DEC_RING / (4 * DEC_PF); ++h) {
+    if (!d.pend_ok) dec_issue(d);
+    dec_commit(d);
+  }
+  while ((int)(d.fillb - d.bpos) < (int)(8 * DEC_NEED_HEAD)) {
+    if (!d.pend_ok) dec_issue(d);
+    dec_commit(d);
+  }
+  if (!d.pend_ok) dec_issue(d);
+  d.set_data(dec_read8_before(d));  // Decoder::new's data (low = 0)
+  dec_gexact<1, 4>(d, m);
+
+  u32 cw = o1_ctx_word(oa.first_row, rows_off, m.lut_bits);  // the row of the next symbol
+  u32 i = 0;
+  // head: single symbols until the output is 64-B aligned
+  constexpr u32 OUT_ALIGN = 16 * DEC_OUT_BURST;
+  static_assert(DEC_OUT_BURST == 4, "bursts of four phases");
+  u32 head = (OUT_ALIGN - ((u32)(uintptr_t)op & (OUT_ALIGN - 1))) & (OUT_ALIGN - 1);
+  if (head > n) head = n;
+  dec_check4<1>(d);
+  for (; i < head; ++i) {
+    op[i] = (uint8_t)o1_dec_sym<DIV>(d, m, map_off, cw);
+    dec_check4<1>(d);
+  }
+  dec_check4<1, DEC_NEED_SPAN>(d);
+  // body: 16-symbol phases, bursts of four, then single ones
+  uint4* ob = reinterpret_cast<uint4*>(op + i);
+  const u32 nfull = (n - i) >> 4;
+  const u32 nbu = nfull / DEC_OUT_BURST;
+  u32 g = 0;  // phase
+#define RC_O1_PHASE(o)                                  \
+  const uint4 o = o1_phase16<DIV>(d, m, map_off, cw);   \
+  ++g;                                                  \
+  dec_phase(d);                                         \
+  dec_check4<1, DEC_NEED_SPAN>(d);
+  for (u32 b = 0; b < nbu; ++b) {
+    rc_prio_rotate(m.prio_rot);
+    RC_O1_PHASE(o0) RC_O1_PHASE(o1) RC_O1_PHASE(o2) RC_O1_PHASE(o3)
+    uint4* ob_b = ob + DEC_OUT_BURST * b;
+    ob_b[0] = o0;
+    ob_b[1] = o1;
+    ob_b[2] = o2;
+    ob_b[3] = o3;
+  }
+  while (g < nfull) {
+    const u32 gb = g;
+    RC_O1_PHASE(o)
+    ob[gb] = o;
+  }
+#undef RC_O1_PHASE
+  i += nfull << 4;
+  for (; i < n; ++i) {
+    op[i] = (uint8_t)o1_dec_sym<DIV>(d, m, map_off, cw);
+    dec_check4<1>(d);
+  }
+  // shift_left_buffer panics once more bytes are needed than the stream holds (decoder.rs:33)
+  if (!d.err && d.bpos > d.limb) d.err = RC_F_TRUNCATED;
+  flags[k] = d.err;
+}
+
+// ------------------------------------------------------------------------------------------
+// Host: the plan and the launchers
+// ------------------------------------------------------------------------------------------
+static u32 o1_bitlen(u32 v) { return v ? 32u - (u32)__builtin_clz(v) : 0u; }
+
+void rc_order1_plan(u32 K, u32 total, SetPlan* p) {
+  // encoder: the set's plan as it is (the map takes the place of the poison row K, which both
+  // layouts reserve at least O1_MAP_BYTES for)
+  rc_set_plan(K, total, p);
+  if (!p->enc_lanes) return;
+  // decoder: rc_set_plan's rule with the map counted beside the rows
+  const u32 bl = o1_bitlen(total - 1);
+  const u32 cap = bl < 12u ? bl : 12u;
+  const u32 tables = K * 4u * SET_ROW_WORDS + O1_MAP_BYTES;
+  auto bits_at = [&](u32 lanes) -> int {
+    const u32 fixed = tables + lanes * SET_DEC_LANE_BYTES;
+    int b = -1;
+    for (u32 t = 0; t <= cap; ++t)
+      if (fixed + K * (4u << t) <= SET_LDS_BYTES) b = (int)t;
+    return b;
+  };
+  u32 best_lanes = 0;
+  int best = -1;
+  for (u32 lanes = 1024; lanes >= 512; lanes -= 256) {
+    const int b = bits_at(lanes);
+    if (b >= (int)(cap < 8u ? cap : 8u)) {
+      best_lanes = lanes;
+      best = b;
+      break;
+    }
+    if (b > best) {
+      best_lanes = lanes;
+      best = b;
+    }
+  }
+  p->dec_lanes = best_lanes;
+  p->dec_bits = (u32)best;
+  p->dec_shift = bl > p->dec_bits ? bl - p->dec_bits : 0u;
+  p->dec_lds = tables + K * (4u << p->dec_bits) + best_lanes * SET_DEC_LANE_BYTES;
+}
+
+hipError_t rc_order1_encode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a_in,
+                                   int div, const SetPlan& p, const uint8_t* syms,
+                                   const u64* sym_off, u32 n_chunks, uint8_t* out,
+                                   const u64* out_off, u64* out_len, u32* flags) {
+  O1Args a = a_in;
+  a.s.tab_bytes = p.enc_tab;
+  hipError_t lds_err = hipSuccess;
+  const u32 lanes = set_launch_lanes(p.enc_lanes, n_chunks);
+  const u32 lds = p.enc_tab + lanes * SET_ENC_LANE_BYTES;
+  const dim3 grid((n_chunks + lanes - 1) / lanes), block(lanes);
+  auto go = [&](auto kern) {
+    if ((lds_err = set_allow_lds(reinterpret_cast<const void*>(kern))) != hipSuccess) return;
+    rc_prio_policy(a.s.m, kPrioEncoder, grid.x,
+                   rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)lanes, lds), k);
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, a, syms, sym_off, n_chunks, out, out_off,
+                       out_len, flags);
+  };
+  if (div == DIV_POW2) {
+    if (p.enc_layout == 0) go(k_encode_order1<DIV_POW2, 0>);
+    else go(k_encode_order1<DIV_POW2, 1>);
+  } else {
+    if (p.enc_layout == 0) go(k_encode_order1<DIV_MAGIC, 0>);
+    else go(k_encode_order1<DIV_MAGIC, 1>);
+  }
+  return lds_err != hipSuccess ? lds_err : hipGetLastError();
+}
+
+hipError_t rc_order1_decode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a_in,
+                                   int div, const SetPlan& p, const uint8_t* code,
+                                   const u64* code_off, const u64* code_len, uint8_t* syms_out,
+                                   const u64* sym_off, u32 n_chunks, u32* flags) {
+  O1Args a = a_in;
+  hipError_t lds_err = hipSuccess;
+  const u32 lanes = set_launch_lanes(p.dec_lanes, n_chunks);
+  const u32 lds = p.dec_lds - (p.dec_lanes - lanes) * SET_DEC_LANE_BYTES;
+  const dim3 grid((n_chunks + lanes - 1) / lanes), block(lanes);
+  auto go = [&](auto kern) {
+    if ((lds_err = set_allow_lds(reinterpret_cast<const void*>(kern))) != hipSuccess) return;
+    rc_prio_policy(a.s.m, kPrioDecoder512, grid.x,
+                   rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)lanes, lds), k);
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, a, code, code_off, code_len, syms_out,
+                       sym_off, n_chunks, flags);
+  };
+  if (div == DIV_POW2) go(k_decode_order1<DIV_POW2>);
+  else go(k_decode_order1<DIV_MAGIC>);
+  return lds_err != hipSuccess ? lds_err : hipGetLastError();
+}

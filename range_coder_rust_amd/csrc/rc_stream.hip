@@ -391,7 +391,7 @@ rc_status rc_encode_host(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
   int dev;
   if (rc_ctx_stream_(ctx, &s0, &dev) != RC_OK || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
   // (model sets and wide models: their own device calls only)
-  if (rc_model_is_set_(m) || rc_model_is_wide_(m)) return RC_E_ARG;
+  if (rc_model_is_set_(m) || rc_model_is_wide_(m) || rc_model_is_order1_(m)) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
@@ -477,7 +477,7 @@ rc_status rc_decode_host(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
   int dev;
   if (rc_ctx_stream_(ctx, &s0, &dev) != RC_OK || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
   // (model sets and wide models: their own device calls only)
-  if (rc_model_is_set_(m) || rc_model_is_wide_(m)) return RC_E_ARG;
+  if (rc_model_is_set_(m) || rc_model_is_wide_(m) || rc_model_is_order1_(m)) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
@@ -602,7 +602,7 @@ rc_status rc_encode_host_multi(rc_ctx* const* ctxs, const rc_model* const* model
   if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
   for (u32 i = 0; i < n_ctx; ++i)
     if (!ctxs[i] || !models[i] || rc_model_is_set_(models[i]) ||
-        rc_model_is_wide_(models[i]))
+        rc_model_is_wide_(models[i]) || rc_model_is_order1_(models[i]))
       return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
     if (sym_off[k + 1] < sym_off[k] || out_off[k + 1] < out_off[k]) return RC_E_ARG;
@@ -627,7 +627,7 @@ rc_status rc_decode_host_multi(rc_ctx* const* ctxs, const rc_model* const* model
   if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
   for (u32 i = 0; i < n_ctx; ++i)
     if (!ctxs[i] || !models[i] || rc_model_is_set_(models[i]) ||
-        rc_model_is_wide_(models[i]))
+        rc_model_is_wide_(models[i]) || rc_model_is_order1_(models[i]))
       return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
     if (sym_off[k + 1] < sym_off[k]) return RC_E_ARG;

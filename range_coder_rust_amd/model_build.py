@@ -9,13 +9,16 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
   quantize_counts_wide(counts, T) the same for up to 4096 symbols (wide static models)
   build_model(syms, sym_off, T)   histogram -> table -> StaticModel, in one call
   ideal_bits(model, chunk_hist)   rc_ideal_bits: per-chunk sum of ideal code lengths (HIP)
+  histogram_order1(syms, sym_off, ctx_map, first_row)   rc_histogram_order1: symbol counts by
+                                  context class, the previous symbol picking the class (HIP)
+  build_order1_set(syms, sym_off, ctx_map)   those counts -> Order1ModelSet, in one call
 """
 import ctypes
 
 import numpy as np
 
 from . import _native as N
-from .api import StaticModel, _check_dev, _ptr, _torch, default_context
+from .api import Order1ModelSet, StaticModel, _check_dev, _ptr, _torch, default_context
 
 
 def quantize_counts(counts, target_total=0, all_symbols=False, _entry="rc_quantize_counts"):
@@ -72,6 +75,58 @@ def build_model(syms, sym_off, target_total=1 << 16, n_symbols=256, all_symbols=
         raise ValueError(f"symbols >= {n_symbols} present")
     c, cum, total = quantize_counts(counts[:n_symbols], target_total, all_symbols)
     return StaticModel(c, cum, total, ctx=ctx or default_context(syms.device.index))
+
+
+def _ctx_map256(ctx_map):
+    cm = np.asarray(ctx_map)
+    if cm.ndim != 1 or len(cm) > 256 or len(cm) < 1:
+        raise ValueError("ctx_map: 1..256 rows, one per previous symbol")
+    if (cm < 0).any() or (cm > 255).any():
+        raise ValueError("ctx_map entries are rows of the set")
+    m = np.zeros(256, np.uint8)  # (symbols past the map: row 0)
+    m[:len(cm)] = cm
+    return m
+
+
+def histogram_order1(syms, sym_off, ctx_map, first_row=0, n_models=None, hist=None, ctx=None):
+    """rc_histogram_order1 on torch tensors (async, torch's current stream): int64[K, 256], row j
+    = the counts of the symbols whose context row is j (first_row for a chunk's first symbol,
+    ctx_map[previous symbol] otherwise).  ctx_map: up to 256 rows (missing entries are row 0);
+    K = n_models (default: the largest row named + 1).  hist: counts are added into it."""
+    torch = _torch()
+    _check_dev(syms, "syms", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    m = _ctx_map256(ctx_map)
+    K = int(n_models) if n_models is not None else max(int(m.max()), int(first_row)) + 1
+    if not 1 <= K <= N.MAX_SET_MODELS or int(m.max()) >= K or not 0 <= int(first_row) < K:
+        raise ValueError(f"ctx_map and first_row must name rows 0..{K - 1} of at most "
+                         f"{N.MAX_SET_MODELS}")
+    ctx = ctx or default_context(syms.device.index)
+    n = sym_off.numel() - 1
+    if hist is None:
+        hist = torch.zeros((K, 256), dtype=torch.int64, device=syms.device)
+    else:
+        _check_dev(hist, "hist", (torch.int64, torch.uint64))
+        if tuple(hist.shape) != (K, 256):
+            raise ValueError(f"hist must be [{K}, 256]")
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_histogram_order1(ctx.handle, K, ctypes.c_void_p(m.ctypes.data),
+                                         int(first_row), _ptr(syms), _ptr(sym_off), n,
+                                         _ptr(hist)), "rc_histogram_order1")
+    return hist
+
+
+def build_order1_set(syms, sym_off, ctx_map, first_row=0, target_total=1 << 16, n_symbols=256,
+                     n_models=None, ctx=None):
+    """Pair counts of the batch on the GPU, then an Order1ModelSet of the rows quantised from
+    them (every symbol kept encodable in every row)."""
+    ctx = ctx or default_context(syms.device.index)
+    hist = histogram_order1(syms, sym_off, ctx_map, first_row, n_models=n_models, ctx=ctx)
+    counts = hist.cpu().numpy().astype(np.uint64)
+    if n_symbols < 256 and counts[:, n_symbols:].any():
+        raise ValueError(f"symbols >= {n_symbols} present")
+    return Order1ModelSet.from_counts(counts[:, :n_symbols], _ctx_map256(ctx_map)[:n_symbols],
+                                      first_row, target_total, ctx=ctx)
 
 
 def ideal_bits(model, chunk_hist):
