@@ -438,6 +438,22 @@ rc_status rc_synth_fill(rc_ctx* ctx, uint64_t seed, const uint8_t* inv_cdf_host,
 rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms_dev, const uint64_t* sym_off_dev,
                        uint32_t n_chunks, uint32_t* chunk_hist_dev, uint64_t* hist_dev);
 
+/* Histogram of 16-bit symbols (device pointers; stream-ordered on the context's stream).
+ * syms16_dev      uint16 symbols, host byte order, 2-byte aligned (else RC_E_ARG);
+ *                 chunk k = [sym_off[k], sym_off[k+1]), offsets in symbols
+ * n_bins          1..RC_MAX_WIDE_SYMBOLS (else RC_E_ARG)
+ * chunk_hist_dev  NULL or n_chunks*n_bins uint32: row k = counts of chunk k (overwritten)
+ * hist_dev        NULL or n_bins uint64: batch counts ADDED into it (zero it first)
+ * oob_dev         NULL or one uint64: the number of symbols >= n_bins (65535 included),
+ *                 ADDED into it; such symbols are counted nowhere else
+ * The batch counts are exact for any batch size.  With all three results NULL the call does
+ * nothing (RC_OK).  Without rows the counters live on chip across a workgroup's chunks; asking
+ * for rows costs a readout of n_bins counters per chunk, which at n_bins = 4096 is the same
+ * order of work as counting a chunk of 16 Ki symbols.                                       */
+rc_status rc_histogram_wide(rc_ctx* ctx, const void* syms16_dev, const uint64_t* sym_off_dev,
+                            uint32_t n_chunks, uint32_t n_bins, uint32_t* chunk_hist_dev,
+                            uint64_t* hist_dev, uint64_t* oob_dev);
+
 /* Pair counts by context class: the counts from which the rows of an order-1 set are quantised
  * (rc_quantize_counts per row, with RC_Q_ALL_SYMBOLS, then rc_model_create_order1_set).
  * hist_dev: n_models x 256 uint64, ADDED into (zero it first).  Row j counts the symbols of all
@@ -475,6 +491,17 @@ rc_status rc_quantize_counts_wide(const uint64_t* counts_host, uint32_t n_symbol
 rc_status rc_ideal_bits(rc_ctx* ctx, const uint32_t* c_freq_host, uint32_t n_symbols,
                         uint32_t total_freq, const uint32_t* chunk_hist_dev, uint32_t n_chunks,
                         double* bits_dev);
+
+/* Batched PModel::ideal_code_length over a wide model, straight from the symbols:
+ * bits_dev[k] = sum over the symbols s of chunk k of log2(total / c[s]), f64.
+ * A symbol with c == 0 or s >= n_symbols makes its chunk +inf; an empty chunk is 0.0.
+ * `wide` must be a wide static model (RC_E_ARG for any other kind).  syms16_dev and
+ * sym_off_dev as in rc_histogram_wide.  Stream-ordered; the call waits for the stream (it reads
+ * the model's table back to price it on the host, as rc_ideal_bits prices its host table).
+ * Accuracy: each chunk is summed as 64 partial sums and a 6-step butterfly, so a finite result
+ * is within about (n_k / 64 + 7) * 2^-53 relative of the exact sum of its n_k terms.        */
+rc_status rc_ideal_bits_wide(rc_ctx* ctx, const rc_model* wide, const void* syms16_dev,
+                             const uint64_t* sym_off_dev, uint32_t n_chunks, double* bits_dev);
 
 /* ---- chunked container "RCB1"  ----
  * The reference's stream carries neither its symbol count (sample_impl.rs:113-120) nor its

@@ -17,6 +17,7 @@ from .api import (  # noqa: F401
 from . import synth  # noqa: F401
 from .model_build import build_model, histogram, ideal_bits, quantize_counts, quantize_counts_wide  # noqa: F401
 from .model_build import build_order1_set, histogram_order1  # noqa: F401
+from .model_build import build_wide_model, histogram_wide, ideal_bits_wide  # noqa: F401
 from . import container  # noqa: F401
 from .container import ContainerError, compress, decompress  # noqa: F401
 

@@ -41,6 +41,7 @@ EXPORTS = (
     "rc_quantize_counts_wide",
     "rc_model_create_order1_set", "rc_encode_batch_order1", "rc_decode_batch_order1",
     "rc_histogram_order1",
+    "rc_histogram_wide", "rc_ideal_bits_wide",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
@@ -156,6 +157,11 @@ def load():
     L.rc_model_order1_check_.restype = _I
     L.rc_model_order1_plan_.argtypes = [_U32, _U32, _P]
     L.rc_model_order1_plan_.restype = _I
+    L.rc_histogram_wide.argtypes = [_P, _P, _P, _U32, _U32, _P, _P, _P]
+    L.rc_ideal_bits_wide.argtypes = [_P, _P, _P, _P, _U32, _P]
+    # host-only hook of the wide histogram (not in the header; tests/test_gpu_wide_build.py)
+    L.rc_histogram_wide_copies_.argtypes = [_U32]
+    L.rc_histogram_wide_copies_.restype = _U32
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error"):
             getattr(L, name).restype = _I

@@ -282,3 +282,6 @@ bool rc_model_is_set_(const rc_model* m);
 bool rc_model_is_wide_(const rc_model* m);
 // likewise for an order-1 set (rc_model_create_order1_set) and the order-1 batch calls
 bool rc_model_is_order1_(const rc_model* m);
+// rc_kernels.hip: a wide static model's cum row (device memory: cum[0 .. n], cum[n] = total), its
+// alphabet size and its device; false for any other kind of model (rc_ideal_bits_wide)
+bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int* device);

@@ -121,6 +121,13 @@ struct rc_model {
 bool rc_model_is_set_(const rc_model* m) { return m && m->kind == RC_KIND_SET; }
 bool rc_model_is_wide_(const rc_model* m) { return m && m->kind == RC_KIND_WIDE; }
 bool rc_model_is_order1_(const rc_model* m) { return m && m->kind == RC_KIND_ORDER1; }
+bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int* device) {
+  if (!m || m->kind != RC_KIND_WIDE) return false;
+  *row = m->wide.row;
+  *n_symbols = m->wide.m.n;
+  *device = m->device;
+  return true;
+}
 
 namespace {
 

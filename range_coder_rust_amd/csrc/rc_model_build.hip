@@ -10,7 +10,9 @@
 //     when no target is given, or a table scaled to a target total (e.g. 2^16, so the coder
 //     takes its fast power-of-two path), deterministic and restated by the oracle;
 //   * k_ideal_bits is the batched PModel::ideal_code_length (pmodel.rs:14-40): per chunk,
-//     sum over its histogram of count * log2(total / c), in f64.
+//     sum over its histogram of count * log2(total / c), in f64;
+//   * k_histogram_wide and k_ideal_bits_wide do both for the 16-bit symbols of wide static
+//     models (up to 4096 bins; the ideal bits straight from the symbols, without a histogram).
 #include "rc_common.h"
 
 #include <math.h>
@@ -258,6 +260,201 @@ __global__ __launch_bounds__(HWG) void k_ideal_bits(const double* __restrict__ i
   }
 }
 
+// ---- wide (16-bit) symbols: the counts and the ideal bits of a wide static model (rc_wide.h) ----
+
+// k_histogram_wide: counts of 16-bit symbols below n_bins <= 4096.  Chunk-stride workgroups of 4
+// waves like k_histogram; 16-B loads of 8 symbols with a symbol-wise head (0..7 symbols up to the
+// first 16-B boundary: a chunk starts at any symbol) and tail around them.  One 16-KiB array of
+// plain u32 LDS counters per workgroup (8 workgroups, 32 waves, per CU: §9.2's finding is that
+// the rate follows the resident waves), shared by its four waves and split into 2^cshift copies
+// of every bin: counter word = (bin << cshift) + (lane & (copies - 1)), so the copies of one bin
+// lie in neighbouring banks and the lanes of one ds_add that hit one bin spread over them.  The
+// host picks the copies from n_bins (hw_copy_shift): as many as fit, at most 32 (an LDS atomic is
+// served in two groups of 32 lanes, and only the lanes of one group conflict), one at 4096 bins.
+// A symbol >= n_bins touches no counter: it is counted by ballot into a count per wave.
+//
+// ROWS = false (batch only): the counters persist across the workgroup's chunks and are read out
+// only at a flush, so no chunk pays a readout of n_bins counters.  ROWS = true: read out and
+// cleared per chunk; at n_bins = 4096 that readout (16 bins per thread and two barriers) is the
+// same order of work as counting a 16-Ki-symbol chunk (64 symbols per thread), which is inherent
+// to asking for rows.  Either way at most 2^32 - 1 symbols are counted between two flushes into
+// the u64 results, so no u32 counter wraps whatever the data (as k_histogram_order1).
+#ifndef HW_WORDS             // (scratch builds: -DHW_WORDS=8192u)
+#define HW_WORDS 4096u       // counter words per workgroup (16 KiB)
+#endif
+#define HW_SEG (1ull << 27)  // 16-B blocks (2^30 symbols) of a chunk between two looks at the budget
+
+static inline u32 hw_copy_shift(u32 n_bins) {  // log2 of the copies: the most that fit, <= 32
+  u32 s = 0;
+  while (s < 5 && ((u64)n_bins << (s + 1)) <= HW_WORDS) ++s;
+  return s;
+}
+
+template <bool ROWS>
+__global__ __launch_bounds__(256) void k_histogram_wide(
+    const uint16_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks, u32 n_bins,
+    u32 cshift, u32* __restrict__ chunk_hist, u64* __restrict__ hist, u64* __restrict__ oob) {
+  __shared__ u32 sh[HW_WORDS];
+  const u32 tid = threadIdx.x, lane = tid & 63;
+  const u32 cmask = (1u << cshift) - 1u, copy = lane & cmask;
+  RC_VGPR_FLOOR_64();
+  for (u32 j = tid; j < HW_WORDS; j += 256) sh[j] = 0;
+  // symbols >= n_bins seen by this wave since the last flush.  Added to from ballots inside
+  // divergent code, so only a lane that took part in every ballot holds the wave's count: lane 0
+  // does (the head, the tail and the block loop give the work to the lowest threads first).
+  u32 oobc = 0;
+  u32 acc[16];  // ROWS: bins tid + 256 j over this workgroup's chunks since the last flush
+#pragma unroll
+  for (u32 j = 0; j < 16; ++j) acc[j] = 0;
+  auto count = [&](u32 s) {
+    const bool in = s < n_bins;
+    oobc += (u32)__builtin_popcountll(__builtin_amdgcn_ballot_w64(!in));
+    if (in) hl_add((hl_u32*)(sh + (s << cshift) + copy), 1u);
+  };
+  // the sum of bin's copies, cleared (a thread reads out bins tid + 256 j only; the rotation
+  // spreads the 32 lanes of a read over the banks)
+  auto take = [&](u32 bin) {
+    u32 v = 0;
+#pragma unroll 1
+    for (u32 c = 0; c <= cmask; ++c) {
+      u32* w = sh + (bin << cshift) + ((c + tid) & cmask);
+      v += *w;
+      *w = 0;
+    }
+    return v;
+  };
+  // into the u64 results: acc (rows) or the counters (batch only), and the out-of-range count
+  auto flush = [&]() {
+    if (ROWS) {
+      u32 t = tid;  // (opaque, as at the readout below)
+      asm volatile("" : "+v"(t));
+#pragma unroll
+      for (u32 j = 0; j < 16; ++j) {
+        if (hist && acc[j])
+          atomicAdd(reinterpret_cast<unsigned long long*>(hist + t + 256 * j),
+                    (unsigned long long)acc[j]);
+        acc[j] = 0;
+      }
+    } else {
+      __syncthreads();
+#pragma unroll 1
+      for (u32 bin = tid; bin < n_bins; bin += 256) {
+        const u32 v = take(bin);
+        if (hist && v)
+          atomicAdd(reinterpret_cast<unsigned long long*>(hist + bin), (unsigned long long)v);
+      }
+    }
+    if (oob && lane == 0 && oobc)
+      atomicAdd(reinterpret_cast<unsigned long long*>(oob), (unsigned long long)oobc);
+    oobc = 0;
+    if (!ROWS) __syncthreads();
+  };
+  u64 pending = 0;  // symbols counted since the last flush (workgroup-uniform)
+  __syncthreads();
+  for (u32 k = blockIdx.x; k < n_chunks; k += gridDim.x) {
+    const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
+    const uint16_t* p = syms + s0;
+    u64 head = ((16 - ((uintptr_t)p & 15)) & 15) >> 1;
+    if (head > n) head = n;
+    const u64 nv = (n - head) >> 3, t0 = head + (nv << 3);
+    const u32x4* v = reinterpret_cast<const u32x4*>(p + head);
+    for (u64 b0 = 0; b0 == 0 || b0 < nv; b0 += HW_SEG) {
+      const u64 b1 = nv - b0 < HW_SEG ? nv : b0 + HW_SEG;
+      const u64 ns = ((b1 - b0) << 3) + (b0 == 0 ? n - (nv << 3) : 0);
+      if (pending + ns > 0xFFFFFFFFull) {
+        flush();
+        pending = 0;
+      }
+      pending += ns;
+      if (b0 == 0) {
+        if (tid < head) count(p[tid]);
+        if (t0 + tid < n) count(p[t0 + tid]);  // < 8 tail symbols
+      }
+#pragma unroll 2
+      for (u64 i = b0 + tid; i < b1; i += 256) {
+        const u32x4 w = gload16(v + i);
+        const u32 ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          count(ws[q] & 0xFFFFu);
+          count(ws[q] >> 16);
+        }
+      }
+      if (ROWS) {  // this segment's counts into the chunk's row (u32) and into acc
+        __syncthreads();
+        u32* row = chunk_hist + (u64)k * n_bins;
+        // (opaque: from tid itself the compiler keeps sixteen bins' worth of addresses in
+        // registers across the chunk loop, 144 VGPRs in all)
+        u32 t = tid;
+        asm volatile("" : "+v"(t));
+#pragma unroll
+        for (u32 j = 0; j < 16; ++j) {
+          const u32 bin = t + 256 * j;
+          if (bin < n_bins) {
+            const u32 c = take(bin);
+            row[bin] = b0 == 0 ? c : row[bin] + c;
+            acc[j] += c;
+          }
+          // one bin at a time: sixteen readouts in flight at once cost the registers of two
+          // resident waves
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+      }
+    }
+  }
+  flush();
+}
+
+// k_ideal_bits_wide: per chunk the sum of icl[s] over its symbols, straight from the symbols: no
+// histogram and no atomics.  icl[0 .. n]: the table's ideal code lengths in f64, +inf where
+// c == 0, and entry n = +inf, which every symbol >= n is clamped to; it is staged in LDS once per
+// workgroup (8 (n + 1) bytes, at most 32 KiB + 8 B).  One wave per chunk, waves striding over the
+// chunks; a lane gathers the icl of its symbols (16-B loads of 8, head and tail as above) into a
+// private f64 sum and a butterfly adds the 64 sums.  Every term is >= 0 or +inf (there is no
+// 0 * inf), so a chunk is +inf or finite, never NaN.  Accuracy: with P = 64 partial sums of at
+// most ceil(n_k / P) + 1 terms each and log2 P butterfly steps, the relative error of a finite
+// chunk of n_k symbols is at most about (n_k / P + log2 P + 1) * 2^-53.
+__global__ __launch_bounds__(HWG) void k_ideal_bits_wide(
+    const double* __restrict__ icl, u32 n_symbols, const uint16_t* __restrict__ syms,
+    const u64* __restrict__ sym_off, u32 n_chunks, double* __restrict__ bits) {
+  extern __shared__ double s_icl[];
+  const u32 lane = threadIdx.x & 63;
+  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  RC_VGPR_FLOOR_64();
+  for (u32 j = threadIdx.x; j <= n_symbols; j += HWG) s_icl[j] = icl[j];
+  __syncthreads();
+  const u32 nw = gridDim.x * (HWG / 64);
+  for (u32 k = blockIdx.x * (HWG / 64) + wave; k < n_chunks; k += nw) {
+    const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
+    const uint16_t* p = syms + s0;
+    u64 head = ((16 - ((uintptr_t)p & 15)) & 15) >> 1;
+    if (head > n) head = n;
+    const u64 nv = (n - head) >> 3, t0 = head + (nv << 3);
+    const u32x4* v = reinterpret_cast<const u32x4*>(p + head);
+    double acc = 0.0;
+    if (lane < head) acc += s_icl[min((u32)p[lane], n_symbols)];
+    if (t0 + lane < n) acc += s_icl[min((u32)p[t0 + lane], n_symbols)];
+#pragma unroll 2
+    for (u64 i = lane; i < nv; i += 64) {
+      const u32x4 w = gload16(v + i);
+      const u32 ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        acc += s_icl[min(ws[q] & 0xFFFFu, n_symbols)];
+        acc += s_icl[min(ws[q] >> 16, n_symbols)];
+      }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+      const u64 x = (u64)__double_as_longlong(acc);
+      const u64 y = ((u64)(u32)__shfl_xor((int)hi32(x), o) << 32) | (u32)__shfl_xor((int)(u32)x, o);
+      acc += __longlong_as_double((long long)y);
+    }
+    if (lane == 0) bits[k] = acc;
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------
@@ -333,6 +530,95 @@ rc_status rc_histogram_order1(rc_ctx* ctx, uint32_t n_models, const uint8_t* ctx
   hipLaunchKernelGGL(k_histogram_order1, dim3(grid), dim3(256), lds, s, map, first_row, n_models,
                      syms, sym_off, n_chunks, hist);
   return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+}
+
+rc_status rc_histogram_wide(rc_ctx* ctx, const void* syms, const uint64_t* sym_off,
+                            uint32_t n_chunks, uint32_t n_bins, uint32_t* chunk_hist,
+                            uint64_t* hist, uint64_t* oob) {
+  hipStream_t s;
+  int dev;
+  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS || n_bins < 1 ||
+      n_bins > RC_MAX_WIDE_SYMBOLS || ((uintptr_t)syms & 1u) != 0)
+    return RC_E_ARG;
+  if (n_chunks == 0 || (!chunk_hist && !hist && !oob)) return RC_OK;
+  if (!syms || !sym_off) return RC_E_ARG;
+  DevSet g(dev);
+  rc_svc_yield_all_();
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return RC_E_DEVICE;
+  // 16 KiB LDS per workgroup: 8 workgroups (32 waves) per CU
+  const u32 grid = std::min<u32>(n_chunks, (u32)cus * std::min(8u, 163840u / (4u * HW_WORDS)));
+  const u32 cshift = hw_copy_shift(n_bins);
+  if (chunk_hist)
+    hipLaunchKernelGGL(k_histogram_wide<true>, dim3(grid), dim3(256), 0, s,
+                       (const uint16_t*)syms, sym_off, n_chunks, n_bins, cshift, chunk_hist, hist,
+                       oob);
+  else
+    hipLaunchKernelGGL(k_histogram_wide<false>, dim3(grid), dim3(256), 0, s,
+                       (const uint16_t*)syms, sym_off, n_chunks, n_bins, cshift, chunk_hist, hist,
+                       oob);
+  return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+}
+
+// Internal test hook (not in include/range_coder.h; host only): the copies of every bin that
+// k_histogram_wide keeps for n_bins bins (0 for an n_bins rc_histogram_wide refuses).
+uint32_t rc_histogram_wide_copies_(uint32_t n_bins) {
+  return n_bins < 1 || n_bins > RC_MAX_WIDE_SYMBOLS ? 0u : 1u << hw_copy_shift(n_bins);
+}
+
+rc_status rc_ideal_bits_wide(rc_ctx* ctx, const rc_model* wide, const void* syms,
+                             const uint64_t* sym_off, uint32_t n_chunks, double* bits) {
+  hipStream_t s;
+  int dev, mdev;
+  const u32* row_dev;
+  u32 n;
+  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (!rc_model_wide_row_(wide, &row_dev, &n, &mdev)) return RC_E_ARG;  // kinds do not mix
+  if (((uintptr_t)syms & 1u) != 0) return RC_E_ARG;  // 16-bit symbols
+  if (n_chunks == 0) return RC_OK;
+  if (!syms || !sym_off || !bits || mdev != dev) return RC_E_ARG;
+  DevSet g(dev);
+  rc_svc_yield_all_();
+  // the model keeps its table on the device only (the cum row cum[0 .. n], cum[n] = total): read
+  // it back, then PModel::ideal_code_length (pmodel.rs:14-40) per symbol exactly as
+  // rc_ideal_bits computes it, +inf for c == 0 and for the entry symbols >= n are clamped to.
+  // Pinned staging: the row, then the table, 8-B aligned.
+  const size_t row_bytes = (((size_t)n + 1) * sizeof(u32) + 7) & ~(size_t)7;
+  const size_t icl_bytes = ((size_t)n + 1) * sizeof(double);
+  char* pin = (char*)rc_pinned_scratch_(row_bytes + icl_bytes);
+  if (!pin) return RC_E_DEVICE;
+  if (hipMemcpyAsync(pin, row_dev, ((size_t)n + 1) * sizeof(u32), hipMemcpyDeviceToHost, s) !=
+          hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return RC_E_DEVICE;
+  const u32* cum = (const u32*)pin;
+  double* icl = (double*)(pin + row_bytes);
+  const double lt = log((double)cum[n]);
+  for (u32 i = 0; i < n; ++i) {
+    const u32 c = cum[i + 1] - cum[i];
+    icl[i] = c > 0 ? (lt - log((double)c)) / M_LN2 : INFINITY;
+  }
+  icl[n] = INFINITY;
+  double* d = nullptr;
+  if (hipMallocAsync((void**)&d, icl_bytes, s) != hipSuccess) return RC_E_DEVICE;
+  if (hipMemcpyAsync(d, icl, icl_bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
+    (void)hipFreeAsync(d, s);
+    return RC_E_DEVICE;
+  }
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 256;
+  // one wave per chunk, waves striding over the chunks; the table's LDS bounds the workgroups
+  // per CU (4 at 4096 symbols), 8 (32 waves) at most
+  const u32 per_cu = std::max(1u, std::min(8u, 163840u / (u32)icl_bytes));
+  const u32 grid = std::min<u32>((n_chunks + HWG / 64 - 1) / (HWG / 64), (u32)cus * per_cu);
+  hipLaunchKernelGGL(k_ideal_bits_wide, dim3(grid), dim3(HWG), icl_bytes, s, d, n,
+                     (const uint16_t*)syms, sym_off, n_chunks, bits);
+  const bool ok = hipGetLastError() == hipSuccess;
+  // the pinned staging is reused by this thread's next call: wait for the copy
+  const bool fr = hipFreeAsync(d, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  return ok && fr ? RC_OK : RC_E_DEVICE;
 }
 
 }  // extern "C"

@@ -12,13 +12,18 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
   histogram_order1(syms, sym_off, ctx_map, first_row)   rc_histogram_order1: symbol counts by
                                   context class, the previous symbol picking the class (HIP)
   build_order1_set(syms, sym_off, ctx_map)   those counts -> Order1ModelSet, in one call
+  histogram_wide(syms, sym_off, n_bins)      rc_histogram_wide: the counts of 16-bit symbols (HIP)
+  build_wide_model(syms, sym_off, n)         those counts -> WideStaticModel, in one call
+  ideal_bits_wide(model, syms, sym_off)      rc_ideal_bits_wide: per-chunk ideal bits of a wide
+                                  model, straight from the symbols (HIP)
 """
 import ctypes
 
 import numpy as np
 
 from . import _native as N
-from .api import Order1ModelSet, StaticModel, _check_dev, _ptr, _torch, default_context
+from .api import (Order1ModelSet, StaticModel, WideStaticModel, _check_dev, _ptr, _sym16, _torch,
+                  default_context)
 
 
 def quantize_counts(counts, target_total=0, all_symbols=False, _entry="rc_quantize_counts"):
@@ -127,6 +132,61 @@ def build_order1_set(syms, sym_off, ctx_map, first_row=0, target_total=1 << 16, 
         raise ValueError(f"symbols >= {n_symbols} present")
     return Order1ModelSet.from_counts(counts[:, :n_symbols], _ctx_map256(ctx_map)[:n_symbols],
                                       first_row, target_total, ctx=ctx)
+
+
+def histogram_wide(syms, sym_off, n_bins, per_chunk=False, batch=True, ctx=None):
+    """rc_histogram_wide on torch tensors (async, torch's current stream): histogram for 16-bit
+    symbols (uint16, or int16 taken as uint16) over bins 0 .. n_bins - 1, n_bins <= 4096.
+
+    Returns (hist, chunk_hist, oob): hist int64[n_bins] (the batch) or None, chunk_hist
+    int32[n, n_bins] (one row per chunk) or None, oob an int64 scalar tensor: the number of
+    symbols >= n_bins, which are counted nowhere else."""
+    torch = _torch()
+    syms = _sym16(syms, "syms")
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= N.MAX_WIDE_SYMBOLS:
+        raise ValueError(f"n_bins must be 1..{N.MAX_WIDE_SYMBOLS}")
+    ctx = ctx or default_context(syms.device.index)
+    n = sym_off.numel() - 1
+    hist = torch.zeros(n_bins, dtype=torch.int64, device=syms.device) if batch else None
+    chunk_hist = (torch.empty((max(n, 1), n_bins), dtype=torch.int32, device=syms.device)
+                  if per_chunk else None)
+    oob = torch.zeros((), dtype=torch.int64, device=syms.device)
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_histogram_wide(ctx.handle, _ptr(syms), _ptr(sym_off), n, n_bins,
+                                       _ptr(chunk_hist), _ptr(hist), _ptr(oob)),
+            "rc_histogram_wide")
+    return hist, (chunk_hist[:n] if per_chunk else None), oob
+
+
+def build_wide_model(syms, sym_off, n_symbols, target_total=1 << 16, all_symbols=True, ctx=None):
+    """Histogram of the batch on the GPU, then a WideStaticModel of its (scaled) table over
+    n_symbols symbols.  ValueError if the batch holds a symbol >= n_symbols."""
+    ctx = ctx or default_context(syms.device.index)
+    hist, _, oob = histogram_wide(syms, sym_off, n_symbols, ctx=ctx)
+    stray = int(oob.item())
+    if stray:
+        raise ValueError(f"{stray} symbols >= {int(n_symbols)} present")
+    counts = hist.cpu().numpy().astype(np.uint64)
+    c, cum, total = quantize_counts_wide(counts, target_total, all_symbols)
+    return WideStaticModel(c, cum, total, ctx=ctx)
+
+
+def ideal_bits_wide(model, syms, sym_off):
+    """rc_ideal_bits_wide: float64[n] tensor, per chunk the sum of log2(total / c[s]) over its
+    16-bit symbols, straight from the symbols (inf if the chunk holds a symbol with c == 0 or
+    one >= model.n_symbols; 0.0 for an empty chunk).  model: a WideStaticModel."""
+    torch = _torch()
+    syms = _sym16(syms, "syms")
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    bits = torch.empty(max(n, 1), dtype=torch.float64, device=syms.device)
+    ctx = model.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_ideal_bits_wide(ctx.handle, model.handle, _ptr(syms), _ptr(sym_off), n,
+                                        _ptr(bits)), "rc_ideal_bits_wide")
+    return bits[:n]
 
 
 def ideal_bits(model, chunk_hist):
