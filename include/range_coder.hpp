@@ -141,6 +141,18 @@ class Context {
   rc_ctx* ctx_ = nullptr;
 };
 
+namespace detail {
+// a slot large enough for n symbols of a table (or tables) with counts c in nearly every case:
+// the worst symbol's bits, 2 % and 64 bytes of slack, a multiple of 16
+inline uint64_t slot_capacity(const std::vector<uint32_t>& c, uint32_t total, uint64_t n) {
+  uint32_t cmin = 0xFFFFFFFFu;
+  for (uint32_t x : c)
+    if (x && x < cmin) cmin = x;
+  const double bits = std::log2((double)total / (double)cmin);
+  return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
+}
+}  // namespace detail
+
 // Device snapshot of a PModel's (c_freq, cum_freq, total_freq) table (rc_model)
 class Model {
  public:
@@ -160,13 +172,7 @@ class Model {
   rc_model* get() const { return m_; }
   Context& ctx() const { return *ctx_; }
   // a slot large enough for n symbols in nearly every case (CAPACITY chunks are retried)
-  uint64_t slot_capacity(uint64_t n) const {
-    uint32_t cmin = 0xFFFFFFFFu;
-    for (uint32_t x : c_)
-      if (x && x < cmin) cmin = x;
-    const double bits = std::log2((double)total_ / (double)cmin);
-    return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
-  }
+  uint64_t slot_capacity(uint64_t n) const { return detail::slot_capacity(c_, total_, n); }
 
  private:
   static std::vector<uint32_t> snapshot_c(const PModel& pm) {
@@ -258,6 +264,121 @@ inline std::vector<std::vector<uint8_t>> decode_chunks(
 #include <hip/hip_runtime_api.h>
 namespace rc {
 
+namespace detail {
+// a device buffer, optionally filled from a host vector (synchronous copies)
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  explicit DevBuf(size_t n) : bytes(n ? n : 1) {
+    if (hipMalloc(&p, bytes) != hipSuccess) throw RangeCoderError("hipMalloc", RC_E_DEVICE);
+  }
+  template <class T>
+  explicit DevBuf(const std::vector<T>& v) : DevBuf(v.size() * sizeof(T)) {
+    if (!v.empty() &&
+        hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(p);
+      throw RangeCoderError("hipMemcpy", RC_E_DEVICE);
+    }
+  }
+  ~DevBuf() { (void)hipFree(p); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  void download(void* dst) const {
+    if (hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+      throw RangeCoderError("hipMemcpy", RC_E_DEVICE);
+  }
+  uint8_t* u8() const { return (uint8_t*)p; }
+  const uint64_t* u64() const { return (const uint64_t*)p; }
+};
+
+// n vectors (part(k), k < n) back to back, at least one element, with their offsets in off[n + 1]
+template <class T, class Part>
+std::vector<T> concat(uint32_t n, Part part, std::vector<uint64_t>& off, size_t spare = 0) {
+  off.assign(n + 1, 0);
+  for (uint32_t k = 0; k < n; ++k) off[k + 1] = off[k] + part(k).size();
+  std::vector<T> all(off[n] + spare ? off[n] + spare : 1);
+  for (uint32_t k = 0; k < n; ++k) std::copy(part(k).begin(), part(k).end(), all.begin() + off[k]);
+  return all;
+}
+
+inline void throw_flagged(const std::vector<uint32_t>& flags) {
+  for (size_t k = 0; k < flags.size(); ++k)
+    if (flags[k])
+      throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
+                            RC_E_CHUNK, flags[k]);
+}
+
+// Encode the chunks of syms (sym_off[n + 1]) into slots of slot(symbols) bytes with one
+// batch(syms_dev, sym_off_dev, n, out_dev, out_off_dev, out_len_dev, flags_dev) call, and once
+// more with exact slots if a chunk overflowed its first one.
+template <class Sym, class Slot, class Batch>
+std::vector<std::vector<uint8_t>> encode_chunks(rc_ctx* ctx, const std::vector<Sym>& syms,
+                                                const std::vector<uint64_t>& sym_off, Slot slot,
+                                                Batch batch) {
+  const uint32_t n = (uint32_t)sym_off.size() - 1;
+  std::vector<uint64_t> cap(n), out_off(n + 1, 0), out_len(n);
+  std::vector<uint32_t> flags(n);
+  for (uint32_t k = 0; k < n; ++k) cap[k] = slot(sym_off[k + 1] - sym_off[k]);
+  DevBuf d_syms(syms), d_soff(sym_off), d_len(8ull * n), d_flags(4ull * n);
+  std::vector<uint8_t> out;
+  for (int attempt = 0; attempt < 2 && n; ++attempt) {
+    for (uint32_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + cap[k];
+    DevBuf d_ooff(out_off), d_out(out_off[n] ? out_off[n] : 1);
+    batch((const Sym*)d_syms.p, d_soff.u64(), n, d_out.u8(), d_ooff.u64(), (uint64_t*)d_len.p,
+          (uint32_t*)d_flags.p);
+    check(rc_ctx_synchronize(ctx), "rc_ctx_synchronize");
+    d_len.download(out_len.data());
+    d_flags.download(flags.data());
+    out.resize(d_out.bytes);
+    d_out.download(out.data());
+    bool retry = false;
+    for (uint32_t k = 0; k < n; ++k)
+      if (flags[k] == RC_F_CAPACITY) {  // exact length is known: retry with it
+        cap[k] = (out_len[k] + 15) & ~(uint64_t)15;
+        retry = true;
+      }
+    if (!retry) break;
+  }
+  throw_flagged(flags);
+  std::vector<std::vector<uint8_t>> res(n);
+  for (uint32_t k = 0; k < n; ++k)
+    res[k].assign(out.begin() + out_off[k], out.begin() + out_off[k] + out_len[k]);
+  return res;
+}
+
+// Decode n streams, code(k) holding count(k) symbols (the count is out-of-band,
+// sample_impl.rs:113-120), with one batch(code_dev, code_off_dev, code_len_dev, syms_dev,
+// sym_off_dev, n, flags_dev) call.
+template <class Sym, class Code, class Count, class Batch>
+std::vector<std::vector<Sym>> decode_chunks(rc_ctx* ctx, uint32_t n, Code code_of, Count count,
+                                            Batch batch) {
+  std::vector<uint64_t> code_off, sym_off(n + 1, 0);
+  const std::vector<uint8_t> code = concat<uint8_t>(n, code_of, code_off, 16);
+  std::vector<uint64_t> code_len(n);
+  std::vector<uint32_t> flags(n);
+  for (uint32_t k = 0; k < n; ++k) {
+    code_len[k] = code_of(k).size();
+    sym_off[k + 1] = sym_off[k] + count(k);
+  }
+  code_off.pop_back();
+  std::vector<Sym> syms(sym_off[n] ? sym_off[n] : 1);
+  if (n) {
+    DevBuf d_code(code), d_coff(code_off), d_clen(code_len), d_soff(sym_off),
+        d_syms(sizeof(Sym) * syms.size()), d_flags(4ull * n);
+    batch(d_code.u8(), d_coff.u64(), d_clen.u64(), (Sym*)d_syms.p, d_soff.u64(), n,
+          (uint32_t*)d_flags.p);
+    check(rc_ctx_synchronize(ctx), "rc_ctx_synchronize");
+    d_flags.download(flags.data());
+    d_syms.download(syms.data());
+  }
+  throw_flagged(flags);
+  std::vector<std::vector<Sym>> res(n);
+  for (uint32_t k = 0; k < n; ++k)
+    res[k].assign(syms.begin() + sym_off[k], syms.begin() + sym_off[k + 1]);
+  return res;
+}
+}  // namespace detail
+
 // A static model set (rc_model_create_static_set): K tables over one alphabet and one
 // total_freq, and batch coding with a model chosen per symbol -- symbol i of a chunk is coded as
 // encoder.encode(&models[idx[i]], sym[i]) and decoded as decoder.decode(&models[idx[i]]).  The
@@ -294,129 +415,48 @@ class ModelSet {
   ModelSet& operator=(const ModelSet&) = delete;
   rc_model* get() const { return m_; }
   Context& ctx() const { return *ctx_; }
-  uint64_t slot_capacity(uint64_t n) const {
-    uint32_t cmin = 0xFFFFFFFFu;
-    for (uint32_t x : c_)
-      if (x && x < cmin) cmin = x;
-    const double bits = std::log2((double)total_ / (double)cmin);
-    return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
-  }
+  uint64_t slot_capacity(uint64_t n) const { return detail::slot_capacity(c_, total_, n); }
 
   // Encode many independent chunks, a model per symbol, in one launch.
   std::vector<std::vector<uint8_t>> encode_chunks(const std::vector<Chunk>& chunks) const {
     const uint32_t n = (uint32_t)chunks.size();
-    std::vector<uint64_t> sym_off(n + 1, 0), cap(n), out_off(n + 1, 0), out_len(n);
-    std::vector<uint32_t> flags(n);
-    for (uint32_t k = 0; k < n; ++k) {
+    for (uint32_t k = 0; k < n; ++k)
       if (chunks[k].data.size() != chunks[k].idx.size())
         throw RangeCoderError("chunk " + std::to_string(k) + ": one index per symbol", RC_E_ARG);
-      sym_off[k + 1] = sym_off[k] + chunks[k].data.size();
-      cap[k] = slot_capacity(chunks[k].data.size());
-    }
-    std::vector<uint8_t> syms(sym_off[n] ? sym_off[n] : 1), idx(syms.size());
-    for (uint32_t k = 0; k < n; ++k) {
-      std::copy(chunks[k].data.begin(), chunks[k].data.end(), syms.begin() + sym_off[k]);
-      std::copy(chunks[k].idx.begin(), chunks[k].idx.end(), idx.begin() + sym_off[k]);
-    }
-    DevBuf d_syms(syms), d_idx(idx), d_soff(sym_off), d_len(8ull * n), d_flags(4ull * n);
-    std::vector<uint8_t> out;
-    for (int attempt = 0; attempt < 2 && n; ++attempt) {
-      for (uint32_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + cap[k];
-      DevBuf d_ooff(out_off), d_out(out_off[n] ? out_off[n] : 1);
-      check(rc_encode_batch_indexed(ctx_->get(), m_, d_syms.u8(), d_idx.u8(), d_soff.u64(), n,
-                                    d_out.u8(), d_ooff.u64(), (uint64_t*)d_len.p,
-                                    (uint32_t*)d_flags.p),
-            "rc_encode_batch_indexed");
-      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
-      d_len.download(out_len.data());
-      d_flags.download(flags.data());
-      out.resize(d_out.bytes);
-      d_out.download(out.data());
-      bool retry = false;
-      for (uint32_t k = 0; k < n; ++k)
-        if (flags[k] == RC_F_CAPACITY) {  // exact length is known: retry with it
-          cap[k] = (out_len[k] + 15) & ~(uint64_t)15;
-          retry = true;
-        }
-      if (!retry) break;
-    }
-    std::vector<std::vector<uint8_t>> res(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      if (flags[k])
-        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
-                              RC_E_CHUNK, flags[k]);
-      res[k].assign(out.begin() + out_off[k], out.begin() + out_off[k] + out_len[k]);
-    }
-    return res;
+    std::vector<uint64_t> sym_off;
+    const auto syms = detail::concat<uint8_t>(
+        n, [&](uint32_t k) -> const std::vector<uint8_t>& { return chunks[k].data; }, sym_off);
+    const detail::DevBuf d_idx(detail::concat<uint8_t>(
+        n, [&](uint32_t k) -> const std::vector<uint8_t>& { return chunks[k].idx; }, sym_off));
+    return detail::encode_chunks(
+        ctx_->get(), syms, sym_off, [&](uint64_t len) { return slot_capacity(len); },
+        [&](const uint8_t* s, const uint64_t* soff, uint32_t nc, uint8_t* out,
+            const uint64_t* ooff, uint64_t* len, uint32_t* flags) {
+          check(rc_encode_batch_indexed(ctx_->get(), m_, s, d_idx.u8(), soff, nc, out, ooff, len,
+                                        flags),
+                "rc_encode_batch_indexed");
+        });
   }
 
   // Decode many independent streams: chunk k gives idx.size() symbols (the count is
   // out-of-band, sample_impl.rs:113-120), symbol i with model idx[i].
   std::vector<std::vector<uint8_t>> decode_chunks(const std::vector<Chunk>& chunks) const {
     const uint32_t n = (uint32_t)chunks.size();
-    std::vector<uint64_t> code_off(n), code_len(n), sym_off(n + 1, 0);
-    std::vector<uint32_t> flags(n);
-    uint64_t tot = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-      code_off[k] = tot;
-      code_len[k] = chunks[k].data.size();
-      tot += chunks[k].data.size();
-      sym_off[k + 1] = sym_off[k] + chunks[k].idx.size();
-    }
-    std::vector<uint8_t> code(tot + 16, 0), idx(sym_off[n] ? sym_off[n] : 1), syms(idx.size());
-    for (uint32_t k = 0; k < n; ++k) {
-      std::copy(chunks[k].data.begin(), chunks[k].data.end(), code.begin() + code_off[k]);
-      std::copy(chunks[k].idx.begin(), chunks[k].idx.end(), idx.begin() + sym_off[k]);
-    }
-    if (n) {
-      DevBuf d_code(code), d_idx(idx), d_coff(code_off), d_clen(code_len), d_soff(sym_off),
-          d_syms(syms.size()), d_flags(4ull * n);
-      check(rc_decode_batch_indexed(ctx_->get(), m_, d_code.u8(), d_coff.u64(), d_clen.u64(),
-                                    d_idx.u8(), d_syms.u8(), d_soff.u64(), n,
-                                    (uint32_t*)d_flags.p),
-            "rc_decode_batch_indexed");
-      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
-      d_flags.download(flags.data());
-      d_syms.download(syms.data());
-    }
-    std::vector<std::vector<uint8_t>> res(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      if (flags[k])
-        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
-                              RC_E_CHUNK, flags[k]);
-      res[k].assign(syms.begin() + sym_off[k], syms.begin() + sym_off[k + 1]);
-    }
-    return res;
+    std::vector<uint64_t> sym_off;
+    const detail::DevBuf d_idx(detail::concat<uint8_t>(
+        n, [&](uint32_t k) -> const std::vector<uint8_t>& { return chunks[k].idx; }, sym_off));
+    return detail::decode_chunks<uint8_t>(
+        ctx_->get(), n, [&](uint32_t k) -> const std::vector<uint8_t>& { return chunks[k].data; },
+        [&](uint32_t k) { return (uint64_t)chunks[k].idx.size(); },
+        [&](const uint8_t* code, const uint64_t* coff, const uint64_t* clen, uint8_t* syms,
+            const uint64_t* soff, uint32_t nc, uint32_t* flags) {
+          check(rc_decode_batch_indexed(ctx_->get(), m_, code, coff, clen, d_idx.u8(), syms, soff,
+                                        nc, flags),
+                "rc_decode_batch_indexed");
+        });
   }
 
  private:
-  friend class WideModel;  // (shares DevBuf)
-  friend class Order1Set;
-  // a device buffer, optionally filled from a host vector (synchronous copies)
-  struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    explicit DevBuf(size_t n) : bytes(n ? n : 1) {
-      if (hipMalloc(&p, bytes) != hipSuccess) throw RangeCoderError("hipMalloc", RC_E_DEVICE);
-    }
-    template <class T>
-    explicit DevBuf(const std::vector<T>& v) : DevBuf(v.size() * sizeof(T)) {
-      if (!v.empty() &&
-          hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(p);
-        throw RangeCoderError("hipMemcpy", RC_E_DEVICE);
-      }
-    }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    void download(void* dst) const {
-      if (hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-        throw RangeCoderError("hipMemcpy", RC_E_DEVICE);
-    }
-    uint8_t* u8() const { return (uint8_t*)p; }
-    const uint64_t* u64() const { return (const uint64_t*)p; }
-  };
   Context* ctx_;
   rc_model* m_ = nullptr;
   std::vector<uint32_t> c_, cum_;
@@ -460,96 +500,38 @@ class Order1Set {
   Order1Set& operator=(const Order1Set&) = delete;
   rc_model* get() const { return m_; }
   Context& ctx() const { return *ctx_; }
-  uint64_t slot_capacity(uint64_t n) const {
-    uint32_t cmin = 0xFFFFFFFFu;
-    for (uint32_t x : c_)
-      if (x && x < cmin) cmin = x;
-    const double bits = std::log2((double)total_ / (double)cmin);
-    return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
-  }
+  uint64_t slot_capacity(uint64_t n) const { return detail::slot_capacity(c_, total_, n); }
 
   // Encode many independent chunks of symbols in one launch.
   std::vector<std::vector<uint8_t>> encode_chunks(
       const std::vector<std::vector<uint8_t>>& chunks) const {
-    using DevBuf = ModelSet::DevBuf;
-    const uint32_t n = (uint32_t)chunks.size();
-    std::vector<uint64_t> sym_off(n + 1, 0), cap(n), out_off(n + 1, 0), out_len(n);
-    std::vector<uint32_t> flags(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      sym_off[k + 1] = sym_off[k] + chunks[k].size();
-      cap[k] = slot_capacity(chunks[k].size());
-    }
-    std::vector<uint8_t> syms(sym_off[n] ? sym_off[n] : 1);
-    for (uint32_t k = 0; k < n; ++k)
-      std::copy(chunks[k].begin(), chunks[k].end(), syms.begin() + sym_off[k]);
-    DevBuf d_syms(syms), d_soff(sym_off), d_len(8ull * n), d_flags(4ull * n);
-    std::vector<uint8_t> out;
-    for (int attempt = 0; attempt < 2 && n; ++attempt) {
-      for (uint32_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + cap[k];
-      DevBuf d_ooff(out_off), d_out(out_off[n] ? out_off[n] : 1);
-      check(rc_encode_batch_order1(ctx_->get(), m_, d_syms.u8(), d_soff.u64(), n, d_out.u8(),
-                                   d_ooff.u64(), (uint64_t*)d_len.p, (uint32_t*)d_flags.p),
-            "rc_encode_batch_order1");
-      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
-      d_len.download(out_len.data());
-      d_flags.download(flags.data());
-      out.resize(d_out.bytes);
-      d_out.download(out.data());
-      bool retry = false;
-      for (uint32_t k = 0; k < n; ++k)
-        if (flags[k] == RC_F_CAPACITY) {  // exact length is known: retry with it
-          cap[k] = (out_len[k] + 15) & ~(uint64_t)15;
-          retry = true;
-        }
-      if (!retry) break;
-    }
-    std::vector<std::vector<uint8_t>> res(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      if (flags[k])
-        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
-                              RC_E_CHUNK, flags[k]);
-      res[k].assign(out.begin() + out_off[k], out.begin() + out_off[k] + out_len[k]);
-    }
-    return res;
+    std::vector<uint64_t> sym_off;
+    const auto syms = detail::concat<uint8_t>(
+        (uint32_t)chunks.size(),
+        [&](uint32_t k) -> const std::vector<uint8_t>& { return chunks[k]; }, sym_off);
+    return detail::encode_chunks(
+        ctx_->get(), syms, sym_off, [&](uint64_t len) { return slot_capacity(len); },
+        [&](const uint8_t* s, const uint64_t* soff, uint32_t nc, uint8_t* out,
+            const uint64_t* ooff, uint64_t* len, uint32_t* flags) {
+          check(rc_encode_batch_order1(ctx_->get(), m_, s, soff, nc, out, ooff, len, flags),
+                "rc_encode_batch_order1");
+        });
   }
 
   // Decode many independent streams: counts[k] symbols from codes[k] (the count is out-of-band,
   // sample_impl.rs:113-120).
   std::vector<std::vector<uint8_t>> decode_chunks(const std::vector<std::vector<uint8_t>>& codes,
                                                   const std::vector<uint64_t>& counts) const {
-    using DevBuf = ModelSet::DevBuf;
     const uint32_t n = (uint32_t)codes.size();
     if (counts.size() != n) throw RangeCoderError("one symbol count per stream", RC_E_ARG);
-    std::vector<uint64_t> code_off(n), code_len(n), sym_off(n + 1, 0);
-    std::vector<uint32_t> flags(n);
-    uint64_t tot = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-      code_off[k] = tot;
-      code_len[k] = codes[k].size();
-      tot += codes[k].size();
-      sym_off[k + 1] = sym_off[k] + counts[k];
-    }
-    std::vector<uint8_t> code(tot + 16, 0), syms(sym_off[n] ? sym_off[n] : 1);
-    for (uint32_t k = 0; k < n; ++k)
-      std::copy(codes[k].begin(), codes[k].end(), code.begin() + code_off[k]);
-    if (n) {
-      DevBuf d_code(code), d_coff(code_off), d_clen(code_len), d_soff(sym_off),
-          d_syms(syms.size()), d_flags(4ull * n);
-      check(rc_decode_batch_order1(ctx_->get(), m_, d_code.u8(), d_coff.u64(), d_clen.u64(),
-                                   d_syms.u8(), d_soff.u64(), n, (uint32_t*)d_flags.p),
-            "rc_decode_batch_order1");
-      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
-      d_flags.download(flags.data());
-      d_syms.download(syms.data());
-    }
-    std::vector<std::vector<uint8_t>> res(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      if (flags[k])
-        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
-                              RC_E_CHUNK, flags[k]);
-      res[k].assign(syms.begin() + sym_off[k], syms.begin() + sym_off[k + 1]);
-    }
-    return res;
+    return detail::decode_chunks<uint8_t>(
+        ctx_->get(), n, [&](uint32_t k) -> const std::vector<uint8_t>& { return codes[k]; },
+        [&](uint32_t k) { return counts[k]; },
+        [&](const uint8_t* code, const uint64_t* coff, const uint64_t* clen, uint8_t* syms,
+            const uint64_t* soff, uint32_t nc, uint32_t* flags) {
+          check(rc_decode_batch_order1(ctx_->get(), m_, code, coff, clen, syms, soff, nc, flags),
+                "rc_decode_batch_order1");
+        });
   }
 
  private:
@@ -589,13 +571,7 @@ class WideModel {
   WideModel& operator=(const WideModel&) = delete;
   rc_model* get() const { return m_; }
   Context& ctx() const { return *ctx_; }
-  uint64_t slot_capacity(uint64_t n) const {
-    uint32_t cmin = 0xFFFFFFFFu;
-    for (uint32_t x : c_)
-      if (x && x < cmin) cmin = x;
-    const double bits = std::log2((double)total_ / (double)cmin);
-    return ((uint64_t)std::ceil(n * bits / 8.0 * 1.02 + 64.0) + 15) & ~(uint64_t)15;
-  }
+  uint64_t slot_capacity(uint64_t n) const { return detail::slot_capacity(c_, total_, n); }
 
   // rc_encode_batch_wide / rc_decode_batch_wide on typed device pointers (asynchronous)
   void encode_batch(const uint16_t* syms_dev, const uint64_t* sym_off_dev, uint32_t n_chunks,
@@ -616,83 +592,30 @@ class WideModel {
   // Encode many independent chunks of 16-bit symbols in one launch.
   std::vector<std::vector<uint8_t>> encode_chunks(
       const std::vector<std::vector<uint16_t>>& chunks) const {
-    typedef ModelSet::DevBuf DevBuf;
-    const uint32_t n = (uint32_t)chunks.size();
-    std::vector<uint64_t> sym_off(n + 1, 0), cap(n), out_off(n + 1, 0), out_len(n);
-    std::vector<uint32_t> flags(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      sym_off[k + 1] = sym_off[k] + chunks[k].size();
-      cap[k] = slot_capacity(chunks[k].size());
-    }
-    std::vector<uint16_t> syms(sym_off[n] ? sym_off[n] : 1);
-    for (uint32_t k = 0; k < n; ++k)
-      std::copy(chunks[k].begin(), chunks[k].end(), syms.begin() + sym_off[k]);
-    DevBuf d_syms(syms), d_soff(sym_off), d_len(8ull * n), d_flags(4ull * n);
-    std::vector<uint8_t> out;
-    for (int attempt = 0; attempt < 2 && n; ++attempt) {
-      for (uint32_t k = 0; k < n; ++k) out_off[k + 1] = out_off[k] + cap[k];
-      DevBuf d_ooff(out_off), d_out(out_off[n] ? out_off[n] : 1);
-      encode_batch((const uint16_t*)d_syms.p, d_soff.u64(), n, d_out.u8(), d_ooff.u64(),
-                   (uint64_t*)d_len.p, (uint32_t*)d_flags.p);
-      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
-      d_len.download(out_len.data());
-      d_flags.download(flags.data());
-      out.resize(d_out.bytes);
-      d_out.download(out.data());
-      bool retry = false;
-      for (uint32_t k = 0; k < n; ++k)
-        if (flags[k] == RC_F_CAPACITY) {  // exact length is known: retry with it
-          cap[k] = (out_len[k] + 15) & ~(uint64_t)15;
-          retry = true;
-        }
-      if (!retry) break;
-    }
-    std::vector<std::vector<uint8_t>> res(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      if (flags[k])
-        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
-                              RC_E_CHUNK, flags[k]);
-      res[k].assign(out.begin() + out_off[k], out.begin() + out_off[k] + out_len[k]);
-    }
-    return res;
+    std::vector<uint64_t> sym_off;
+    const auto syms = detail::concat<uint16_t>(
+        (uint32_t)chunks.size(),
+        [&](uint32_t k) -> const std::vector<uint16_t>& { return chunks[k]; }, sym_off);
+    return detail::encode_chunks(
+        ctx_->get(), syms, sym_off, [&](uint64_t len) { return slot_capacity(len); },
+        [&](const uint16_t* s, const uint64_t* soff, uint32_t nc, uint8_t* out,
+            const uint64_t* ooff, uint64_t* len, uint32_t* flags) {
+          encode_batch(s, soff, nc, out, ooff, len, flags);
+        });
   }
 
   // Decode many independent streams; counts[k] symbols each (out-of-band,
   // sample_impl.rs:113-120)
   std::vector<std::vector<uint16_t>> decode_chunks(const std::vector<std::vector<uint8_t>>& codes,
                                                    const std::vector<uint64_t>& counts) const {
-    typedef ModelSet::DevBuf DevBuf;
-    const uint32_t n = (uint32_t)codes.size();
-    std::vector<uint64_t> code_off(n), code_len(n), sym_off(n + 1, 0);
-    std::vector<uint32_t> flags(n);
-    uint64_t tot = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-      code_off[k] = tot;
-      code_len[k] = codes[k].size();
-      tot += codes[k].size();
-      sym_off[k + 1] = sym_off[k] + counts.at(k);
-    }
-    std::vector<uint8_t> code(tot + 16, 0);
-    std::vector<uint16_t> syms(sym_off[n] ? sym_off[n] : 1);
-    for (uint32_t k = 0; k < n; ++k)
-      std::copy(codes[k].begin(), codes[k].end(), code.begin() + code_off[k]);
-    if (n) {
-      DevBuf d_code(code), d_coff(code_off), d_clen(code_len), d_soff(sym_off),
-          d_syms(2 * syms.size()), d_flags(4ull * n);
-      decode_batch(d_code.u8(), d_coff.u64(), d_clen.u64(), (uint16_t*)d_syms.p, d_soff.u64(), n,
-                   (uint32_t*)d_flags.p);
-      check(rc_ctx_synchronize(ctx_->get()), "rc_ctx_synchronize");
-      d_flags.download(flags.data());
-      d_syms.download(syms.data());
-    }
-    std::vector<std::vector<uint16_t>> res(n);
-    for (uint32_t k = 0; k < n; ++k) {
-      if (flags[k])
-        throw RangeCoderError("chunk " + std::to_string(k) + ": " + flag_string(flags[k]),
-                              RC_E_CHUNK, flags[k]);
-      res[k].assign(syms.begin() + sym_off[k], syms.begin() + sym_off[k + 1]);
-    }
-    return res;
+    return detail::decode_chunks<uint16_t>(
+        ctx_->get(), (uint32_t)codes.size(),
+        [&](uint32_t k) -> const std::vector<uint8_t>& { return codes[k]; },
+        [&](uint32_t k) { return counts.at(k); },
+        [&](const uint8_t* code, const uint64_t* coff, const uint64_t* clen, uint16_t* syms,
+            const uint64_t* soff, uint32_t nc, uint32_t* flags) {
+          decode_batch(code, coff, clen, syms, soff, nc, flags);
+        });
   }
 
  private:

@@ -652,397 +652,6 @@ def slot_capacity(n_symbols, bits_per_symbol, slack=1.02):
     return int(math.ceil((n_symbols * bits_per_symbol / 8.0) * slack + 64)) + 15 & ~15
 
 
-def encode_batch(model, syms, sym_off, out, out_off, out_len=None, flags=None):
-    """rc_encode_batch on torch tensors (async on torch's current stream).
-
-    syms uint8[...]; sym_off int64/uint64[n+1]; out uint8[...]; out_off int64/uint64[n+1].
-    Returns (out_len int64[n], flags int32[n]) device tensors."""
-    torch = _torch()
-    _check_dev(syms, "syms", (torch.uint8,))
-    _check_dev(out, "out", (torch.uint8,))
-    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
-    _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
-    n = sym_off.numel() - 1
-    if out_off.numel() != n + 1:
-        raise ValueError("out_off must have n_chunks + 1 entries")
-    if out_len is None:
-        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=syms.device)
-    if flags is None:
-        flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
-    ctx = model.ctx
-    ctx.bind_stream()
-    N.check(ctx._lib.rc_encode_batch(ctx.handle, model.handle, _ptr(syms), _ptr(sym_off), n,
-                                     _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(flags)),
-            "rc_encode_batch")
-    return out_len[:n], flags[:n]
-
-
-def decode_batch(model, code, code_off, code_len, syms_out, sym_off, flags=None):
-    """rc_decode_batch on torch tensors (async on torch's current stream).  Returns flags."""
-    torch = _torch()
-    _check_dev(code, "code", (torch.uint8,))
-    _check_dev(syms_out, "syms_out", (torch.uint8,))
-    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
-        _check_dev(t, name, (torch.int64, torch.uint64))
-    n = sym_off.numel() - 1
-    if code_off.numel() < n or code_len.numel() < n:
-        raise ValueError("code_off/code_len need n_chunks entries")
-    if flags is None:
-        flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
-    ctx = model.ctx
-    ctx.bind_stream()
-    N.check(ctx._lib.rc_decode_batch(ctx.handle, model.handle, _ptr(code), _ptr(code_off),
-                                     _ptr(code_len), _ptr(syms_out), _ptr(sym_off), n,
-                                     _ptr(flags)), "rc_decode_batch")
-    return flags[:n]
-
-
-def encode_chunks(model, chunks, raise_on_error=True):
-    """Encode a list of symbol sequences (bytes / uint8 arrays), one chunk each.
-
-    Host-resident convenience: uploads, encodes on the GPU, re-encodes chunks that overflowed
-    their first slot with their exact length, downloads.  Returns a list of bytes."""
-    torch = _torch()
-    dev = torch.device("cuda", model.ctx.device)
-    arrs = [np.frombuffer(bytes(c), dtype=np.uint8) if not isinstance(c, np.ndarray)
-            else np.ascontiguousarray(c, dtype=np.uint8) for c in chunks]
-    n = len(arrs)
-    if n == 0:
-        return []
-    lens = np.array([len(a) for a in arrs], dtype=np.int64)
-    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk (use Encoder for longer "
-                                f"streams)")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(lens)
-    bits = model.max_bits_per_symbol()
-    caps = np.array([slot_capacity(int(L), bits) for L in lens], dtype=np.int64)
-    syms_d = torch.from_numpy(np.concatenate(arrs) if sym_off[-1] else np.zeros(1, np.uint8)).to(dev)
-    soff_d = torch.from_numpy(sym_off).to(dev)
-    for attempt in range(2):
-        out_off = np.zeros(n + 1, dtype=np.int64)
-        out_off[1:] = np.cumsum(caps)
-        out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
-        ool_d = torch.from_numpy(out_off).to(dev)
-        out_len, flags = encode_batch(model, syms_d, soff_d, out_d, ool_d)
-        fl = flags.cpu().numpy()
-        ol = out_len.cpu().numpy()
-        if attempt == 0 and np.any(fl == N.F_CAPACITY):
-            caps = np.where(fl == N.F_CAPACITY, (ol + 15) // 16 * 16, caps)
-            continue
-        break
-    host = out_d.cpu().numpy()
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]))
-    return res
-
-
-def decode_chunks(model, codes, counts, raise_on_error=True):
-    """Decode a list of code streams; counts[k] symbols each (the count is out-of-band,
-    as in the reference: sample_impl.rs:113-120).  Returns a list of uint8 numpy arrays."""
-    torch = _torch()
-    dev = torch.device("cuda", model.ctx.device)
-    n = len(codes)
-    if n == 0:
-        return []
-    codes = [bytes(c) for c in codes]
-    clen = np.array([len(c) for c in codes], dtype=np.int64)
-    coff = np.zeros(n, dtype=np.int64)
-    coff[1:] = np.cumsum(clen)[:-1]
-    counts = np.asarray(counts, dtype=np.int64)
-    if int(counts.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(counts.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk (use Decoder for longer "
-                                f"streams)")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(counts)
-    blob = np.frombuffer(b"".join(codes) + b"\0" * 16, dtype=np.uint8)
-    code_d = torch.from_numpy(blob.copy()).to(dev)
-    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.uint8, device=dev)
-    flags = decode_batch(model, code_d, torch.from_numpy(coff).to(dev),
-                         torch.from_numpy(clen).to(dev), syms_d, torch.from_numpy(sym_off).to(dev))
-    fl = flags.cpu().numpy()
-    host = syms_d.cpu().numpy()
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(host[sym_off[k]: sym_off[k + 1]].copy())
-    return res
-
-
-# ------------------------------------------------------------- batch API, a model per symbol
-def encode_batch_indexed(model_set, syms, idx, sym_off, out, out_off, out_len=None, flags=None):
-    """rc_encode_batch_indexed on torch tensors (async on torch's current stream): encode_batch
-    with idx uint8[...], one row of model_set per symbol, indexed like syms.
-    Returns (out_len int64[n], flags int32[n]) device tensors."""
-    torch = _torch()
-    _check_dev(syms, "syms", (torch.uint8,))
-    _check_dev(idx, "idx", (torch.uint8,))
-    _check_dev(out, "out", (torch.uint8,))
-    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
-    _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
-    # (idx is indexed exactly like syms, so a tensor as long as syms covers every read)
-    if idx.numel() < syms.numel():
-        raise ValueError("idx must hold one index per symbol: at least syms.numel() entries")
-    n = sym_off.numel() - 1
-    if out_off.numel() != n + 1:
-        raise ValueError("out_off must have n_chunks + 1 entries")
-    if out_len is None:
-        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=syms.device)
-    if flags is None:
-        flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
-    ctx = model_set.ctx
-    ctx.bind_stream()
-    N.check(ctx._lib.rc_encode_batch_indexed(ctx.handle, model_set.handle, _ptr(syms), _ptr(idx),
-                                             _ptr(sym_off), n, _ptr(out), _ptr(out_off),
-                                             _ptr(out_len), _ptr(flags)),
-            "rc_encode_batch_indexed")
-    return out_len[:n], flags[:n]
-
-
-def decode_batch_indexed(model_set, code, code_off, code_len, idx, syms_out, sym_off, flags=None):
-    """rc_decode_batch_indexed on torch tensors (async on torch's current stream): decode_batch
-    with idx uint8[...], one row of model_set per symbol, indexed like syms_out.  Returns flags."""
-    torch = _torch()
-    _check_dev(code, "code", (torch.uint8,))
-    _check_dev(idx, "idx", (torch.uint8,))
-    _check_dev(syms_out, "syms_out", (torch.uint8,))
-    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
-        _check_dev(t, name, (torch.int64, torch.uint64))
-    # (idx is indexed exactly like syms_out, so a tensor as long as syms_out covers every read)
-    if idx.numel() < syms_out.numel():
-        raise ValueError("idx must hold one index per symbol: at least syms_out.numel() entries")
-    n = sym_off.numel() - 1
-    if code_off.numel() < n or code_len.numel() < n:
-        raise ValueError("code_off/code_len need n_chunks entries")
-    if flags is None:
-        flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
-    ctx = model_set.ctx
-    ctx.bind_stream()
-    N.check(ctx._lib.rc_decode_batch_indexed(ctx.handle, model_set.handle, _ptr(code),
-                                             _ptr(code_off), _ptr(code_len), _ptr(idx),
-                                             _ptr(syms_out), _ptr(sym_off), n, _ptr(flags)),
-            "rc_decode_batch_indexed")
-    return flags[:n]
-
-
-def _u8_chunk(c):
-    return (np.frombuffer(bytes(c), dtype=np.uint8) if not isinstance(c, np.ndarray)
-            else np.ascontiguousarray(c, dtype=np.uint8))
-
-
-def encode_chunks_indexed(model_set, chunks, raise_on_error=True):
-    """encode_chunks over a list of (symbols, indexes) pairs (bytes / uint8 arrays of equal
-    length), one chunk each: symbol i is coded with row indexes[i].  Returns a list of bytes."""
-    torch = _torch()
-    dev = torch.device("cuda", model_set.ctx.device)
-    pairs = [(_u8_chunk(s), _u8_chunk(x)) for s, x in chunks]
-    n = len(pairs)
-    if n == 0:
-        return []
-    for k, (s, x) in enumerate(pairs):
-        if len(s) != len(x):
-            raise ValueError(f"chunk {k}: {len(s)} symbols, {len(x)} indexes")
-    lens = np.array([len(s) for s, _ in pairs], dtype=np.int64)
-    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(lens)
-    bits = model_set.max_bits_per_symbol()
-    caps = np.array([slot_capacity(int(L), bits) for L in lens], dtype=np.int64)
-    cat = (lambda j: np.concatenate([p[j] for p in pairs]) if sym_off[-1]
-           else np.zeros(1, np.uint8))
-    syms_d = torch.from_numpy(cat(0)).to(dev)
-    idx_d = torch.from_numpy(cat(1)).to(dev)
-    soff_d = torch.from_numpy(sym_off).to(dev)
-    for attempt in range(2):
-        out_off = np.zeros(n + 1, dtype=np.int64)
-        out_off[1:] = np.cumsum(caps)
-        out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
-        out_len, flags = encode_batch_indexed(model_set, syms_d, idx_d, soff_d, out_d,
-                                              torch.from_numpy(out_off).to(dev))
-        fl = flags.cpu().numpy()
-        ol = out_len.cpu().numpy()
-        if attempt == 0 and np.any(fl == N.F_CAPACITY):
-            caps = np.where(fl == N.F_CAPACITY, (ol + 15) // 16 * 16, caps)
-            continue
-        break
-    host = out_d.cpu().numpy()
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]))
-    return res
-
-
-def decode_chunks_indexed(model_set, chunks, raise_on_error=True):
-    """decode_chunks over a list of (code, indexes) pairs: chunk k decodes len(indexes) symbols,
-    symbol i with row indexes[i].  Returns a list of uint8 numpy arrays."""
-    torch = _torch()
-    dev = torch.device("cuda", model_set.ctx.device)
-    n = len(chunks)
-    if n == 0:
-        return []
-    codes = [bytes(c) for c, _ in chunks]
-    idxs = [_u8_chunk(x) for _, x in chunks]
-    clen = np.array([len(c) for c in codes], dtype=np.int64)
-    coff = np.zeros(n, dtype=np.int64)
-    coff[1:] = np.cumsum(clen)[:-1]
-    counts = np.array([len(x) for x in idxs], dtype=np.int64)
-    if int(counts.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(counts.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(counts)
-    blob = np.frombuffer(b"".join(codes) + b"\0" * 16, dtype=np.uint8)
-    code_d = torch.from_numpy(blob.copy()).to(dev)
-    idx_d = torch.from_numpy(np.concatenate(idxs) if sym_off[-1]
-                             else np.zeros(1, np.uint8)).to(dev)
-    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.uint8, device=dev)
-    flags = decode_batch_indexed(model_set, code_d, torch.from_numpy(coff).to(dev),
-                                 torch.from_numpy(clen).to(dev), idx_d, syms_d,
-                                 torch.from_numpy(sym_off).to(dev))
-    fl = flags.cpu().numpy()
-    host = syms_d.cpu().numpy()
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(host[sym_off[k]: sym_off[k + 1]].copy())
-    return res
-
-
-# ------------------------------------------------- batch API, the previous symbol picks the model
-def encode_batch_order1(o1_set, syms, sym_off, out, out_off, out_len=None, flags=None):
-    """rc_encode_batch_order1 on torch tensors (async on torch's current stream): encode_batch
-    against an Order1ModelSet, the row of each symbol chosen by the chunk's previous symbol.
-    Returns (out_len int64[n], flags int32[n]) device tensors."""
-    torch = _torch()
-    _check_dev(syms, "syms", (torch.uint8,))
-    _check_dev(out, "out", (torch.uint8,))
-    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
-    _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
-    n = sym_off.numel() - 1
-    if out_off.numel() != n + 1:
-        raise ValueError("out_off must have n_chunks + 1 entries")
-    if out_len is None:
-        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=syms.device)
-    if flags is None:
-        flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
-    ctx = o1_set.ctx
-    ctx.bind_stream()
-    N.check(ctx._lib.rc_encode_batch_order1(ctx.handle, o1_set.handle, _ptr(syms), _ptr(sym_off),
-                                            n, _ptr(out), _ptr(out_off), _ptr(out_len),
-                                            _ptr(flags)), "rc_encode_batch_order1")
-    return out_len[:n], flags[:n]
-
-
-def decode_batch_order1(o1_set, code, code_off, code_len, syms_out, sym_off, flags=None):
-    """rc_decode_batch_order1 on torch tensors (async on torch's current stream): decode_batch
-    against an Order1ModelSet, the row of each symbol chosen by the previous decoded symbol.
-    Returns flags."""
-    torch = _torch()
-    _check_dev(code, "code", (torch.uint8,))
-    _check_dev(syms_out, "syms_out", (torch.uint8,))
-    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
-        _check_dev(t, name, (torch.int64, torch.uint64))
-    n = sym_off.numel() - 1
-    if code_off.numel() < n or code_len.numel() < n:
-        raise ValueError("code_off/code_len need n_chunks entries")
-    if flags is None:
-        flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
-    ctx = o1_set.ctx
-    ctx.bind_stream()
-    N.check(ctx._lib.rc_decode_batch_order1(ctx.handle, o1_set.handle, _ptr(code),
-                                            _ptr(code_off), _ptr(code_len), _ptr(syms_out),
-                                            _ptr(sym_off), n, _ptr(flags)),
-            "rc_decode_batch_order1")
-    return flags[:n]
-
-
-def encode_chunks_order1(o1_set, chunks, raise_on_error=True):
-    """encode_chunks over a list of symbol chunks (bytes / uint8 arrays) against an
-    Order1ModelSet.  Returns a list of bytes."""
-    torch = _torch()
-    dev = torch.device("cuda", o1_set.ctx.device)
-    chunks = [_u8_chunk(c) for c in chunks]
-    n = len(chunks)
-    if n == 0:
-        return []
-    lens = np.array([len(c) for c in chunks], dtype=np.int64)
-    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(lens)
-    bits = o1_set.max_bits_per_symbol()
-    caps = np.array([slot_capacity(int(L), bits) for L in lens], dtype=np.int64)
-    syms_d = torch.from_numpy(np.concatenate(chunks) if sym_off[-1]
-                              else np.zeros(1, np.uint8)).to(dev)
-    soff_d = torch.from_numpy(sym_off).to(dev)
-    for attempt in range(2):
-        out_off = np.zeros(n + 1, dtype=np.int64)
-        out_off[1:] = np.cumsum(caps)
-        out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
-        out_len, flags = encode_batch_order1(o1_set, syms_d, soff_d, out_d,
-                                             torch.from_numpy(out_off).to(dev))
-        fl = flags.cpu().numpy()
-        ol = out_len.cpu().numpy()
-        if attempt == 0 and np.any(fl == N.F_CAPACITY):
-            caps = np.where(fl == N.F_CAPACITY, (ol + 15) // 16 * 16, caps)
-            continue
-        break
-    host = out_d.cpu().numpy()
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]))
-    return res
-
-
-def decode_chunks_order1(o1_set, codes, counts, raise_on_error=True):
-    """decode_chunks against an Order1ModelSet: counts[k] symbols from codes[k] (the count is
-    out-of-band, as in the reference).  Returns a list of uint8 numpy arrays."""
-    torch = _torch()
-    dev = torch.device("cuda", o1_set.ctx.device)
-    n = len(codes)
-    if n == 0:
-        return []
-    codes = [bytes(c) for c in codes]
-    clen = np.array([len(c) for c in codes], dtype=np.int64)
-    coff = np.zeros(n, dtype=np.int64)
-    coff[1:] = np.cumsum(clen)[:-1]
-    counts = np.asarray(counts, dtype=np.int64)
-    if int(counts.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(counts.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(counts)
-    blob = np.frombuffer(b"".join(codes) + b"\0" * 16, dtype=np.uint8)
-    code_d = torch.from_numpy(blob.copy()).to(dev)
-    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.uint8, device=dev)
-    flags = decode_batch_order1(o1_set, code_d, torch.from_numpy(coff).to(dev),
-                                torch.from_numpy(clen).to(dev), syms_d,
-                                torch.from_numpy(sym_off).to(dev))
-    fl = flags.cpu().numpy()
-    host = syms_d.cpu().numpy()
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(host[sym_off[k]: sym_off[k + 1]].copy())
-    return res
-
-
-# --------------------------------------------------------------- batch API, 16-bit symbols
 def _sym16(t, name):
     """A uint16 symbol tensor (int16 tensors are viewed as uint16: the bits are the symbols)."""
     torch = _torch()
@@ -1051,15 +660,26 @@ def _sym16(t, name):
     return t
 
 
-def encode_batch_wide(model, syms, sym_off, out, out_off, out_len=None, flags=None):
-    """rc_encode_batch_wide on torch tensors (async on torch's current stream): encode_batch with
-    syms uint16[...] (int16 is taken as uint16) against a WideStaticModel; sym_off counts symbols.
-    Returns (out_len int64[n], flags int32[n]) device tensors."""
+def _check_syms(t, name, wide):
+    if wide:
+        _sym16(t, name)
+    else:
+        _check_dev(t, name, (_torch().uint8,))
+
+
+def _encode_batch(native, model, syms, idx, sym_off, out, out_off, out_len, flags, wide=False):
+    """The four encode_batch* calls: the checks, the result tensors, the stream and the native
+    call `native` (idx: None, or the index stream that follows syms in its arguments)."""
     torch = _torch()
-    syms = _sym16(syms, "syms")
+    _check_syms(syms, "syms", wide)
+    if idx is not None:
+        _check_dev(idx, "idx", (torch.uint8,))
     _check_dev(out, "out", (torch.uint8,))
     _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
     _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
+    # (idx is indexed exactly like syms, so a tensor as long as syms covers every read)
+    if idx is not None and idx.numel() < syms.numel():
+        raise ValueError("idx must hold one index per symbol: at least syms.numel() entries")
     n = sym_off.numel() - 1
     if out_off.numel() != n + 1:
         raise ValueError("out_off must have n_chunks + 1 entries")
@@ -1069,20 +689,26 @@ def encode_batch_wide(model, syms, sym_off, out, out_off, out_len=None, flags=No
         flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
     ctx = model.ctx
     ctx.bind_stream()
-    N.check(ctx._lib.rc_encode_batch_wide(ctx.handle, model.handle, _ptr(syms), _ptr(sym_off), n,
-                                          _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(flags)),
-            "rc_encode_batch_wide")
+    side = () if idx is None else (_ptr(idx),)
+    N.check(getattr(ctx._lib, native)(ctx.handle, model.handle, _ptr(syms), *side, _ptr(sym_off),
+                                      n, _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(flags)),
+            native)
     return out_len[:n], flags[:n]
 
 
-def decode_batch_wide(model, code, code_off, code_len, syms_out, sym_off, flags=None):
-    """rc_decode_batch_wide on torch tensors (async on torch's current stream): decode_batch into
-    syms_out uint16[...] (or int16, written as uint16).  Returns flags."""
+def _decode_batch(native, model, code, code_off, code_len, idx, syms_out, sym_off, flags,
+                  wide=False):
+    """The four decode_batch* calls (idx: None, or the index stream that follows code_len)."""
     torch = _torch()
     _check_dev(code, "code", (torch.uint8,))
-    syms_out = _sym16(syms_out, "syms_out")
+    if idx is not None:
+        _check_dev(idx, "idx", (torch.uint8,))
+    _check_syms(syms_out, "syms_out", wide)
     for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
         _check_dev(t, name, (torch.int64, torch.uint64))
+    # (idx is indexed exactly like syms_out, so a tensor as long as syms_out covers every read)
+    if idx is not None and idx.numel() < syms_out.numel():
+        raise ValueError("idx must hold one index per symbol: at least syms_out.numel() entries")
     n = sym_off.numel() - 1
     if code_off.numel() < n or code_len.numel() < n:
         raise ValueError("code_off/code_len need n_chunks entries")
@@ -1090,10 +716,16 @@ def decode_batch_wide(model, code, code_off, code_len, syms_out, sym_off, flags=
         flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
     ctx = model.ctx
     ctx.bind_stream()
-    N.check(ctx._lib.rc_decode_batch_wide(ctx.handle, model.handle, _ptr(code), _ptr(code_off),
-                                          _ptr(code_len), _ptr(syms_out), _ptr(sym_off), n,
-                                          _ptr(flags)), "rc_decode_batch_wide")
+    side = () if idx is None else (_ptr(idx),)
+    N.check(getattr(ctx._lib, native)(ctx.handle, model.handle, _ptr(code), _ptr(code_off),
+                                      _ptr(code_len), *side, _ptr(syms_out), _ptr(sym_off), n,
+                                      _ptr(flags)), native)
     return flags[:n]
+
+
+def _u8_chunk(c):
+    return (np.frombuffer(bytes(c), dtype=np.uint8) if not isinstance(c, np.ndarray)
+            else np.ascontiguousarray(c, dtype=np.uint8))
 
 
 def _u16_chunk(c):
@@ -1103,32 +735,48 @@ def _u16_chunk(c):
     return np.ascontiguousarray(a, dtype=np.uint16).reshape(-1)
 
 
-def encode_chunks_wide(model, chunks, raise_on_error=True):
-    """encode_chunks over a list of 16-bit symbol sequences (uint16 arrays or lists of ints), one
-    chunk each, against a WideStaticModel.  Returns a list of bytes."""
+def _offsets(lens, hint):
+    """int64 [0, cumsum(lens)] of a batch's chunk lengths (ChunkTooLongError past the limit)."""
+    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
+        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
+                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk{hint}")
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(lens)
+    return off
+
+
+def _to_dev(arrs, total, dev):
+    """The chunks' arrays back to back on the device (uint16 travels as int16, bit for bit)."""
+    cat = np.concatenate(arrs) if total else np.zeros(1, arrs[0].dtype)
+    return _torch().from_numpy(cat.view(np.int16) if cat.dtype == np.uint16 else cat).to(dev)
+
+
+def _raise_flagged(fl):
+    for k in np.flatnonzero(fl):
+        _raise_for_flag(int(fl[k]), f"chunk {k}")
+
+
+def _encode_chunks(batch, model, arrs, idxs, raise_on_error, hint=""):
+    """The four encode_chunks*: upload, encode with `batch`, encode once more with exact slots if
+    a chunk overflowed its first one, download.  arrs: one symbol array per chunk (uint8 or
+    uint16); idxs: None, or one index array per chunk for batch's idx argument."""
     torch = _torch()
     dev = torch.device("cuda", model.ctx.device)
-    arrs = [_u16_chunk(c) for c in chunks]
     n = len(arrs)
     if n == 0:
         return []
-    lens = np.array([len(a) for a in arrs], dtype=np.int64)
-    if int(lens.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(lens.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(lens)
+    sym_off = _offsets(np.array([len(a) for a in arrs], dtype=np.int64), hint)
     bits = model.max_bits_per_symbol()
-    caps = np.array([slot_capacity(int(L), bits) for L in lens], dtype=np.int64)
-    cat = np.concatenate(arrs) if sym_off[-1] else np.zeros(1, np.uint16)
-    syms_d = torch.from_numpy(cat.view(np.int16)).to(dev)
+    caps = np.array([slot_capacity(int(L), bits) for L in np.diff(sym_off)], dtype=np.int64)
+    ins = (_to_dev(arrs, sym_off[-1], dev),)
+    if idxs is not None:
+        ins += (_to_dev(idxs, sym_off[-1], dev),)
     soff_d = torch.from_numpy(sym_off).to(dev)
     for attempt in range(2):
         out_off = np.zeros(n + 1, dtype=np.int64)
         out_off[1:] = np.cumsum(caps)
         out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
-        out_len, flags = encode_batch_wide(model, syms_d, soff_d, out_d,
-                                           torch.from_numpy(out_off).to(dev))
+        out_len, flags = batch(model, *ins, soff_d, out_d, torch.from_numpy(out_off).to(dev))
         fl = flags.cpu().numpy()
         ol = out_len.cpu().numpy()
         if attempt == 0 and np.any(fl == N.F_CAPACITY):
@@ -1136,17 +784,14 @@ def encode_chunks_wide(model, chunks, raise_on_error=True):
             continue
         break
     host = out_d.cpu().numpy()
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]))
-    return res
+    if raise_on_error:
+        _raise_flagged(fl)
+    return [bytes(host[out_off[k]: out_off[k] + min(ol[k], caps[k])]) for k in range(n)]
 
 
-def decode_chunks_wide(model, codes, counts, raise_on_error=True):
-    """decode_chunks against a WideStaticModel; counts[k] symbols each.  Returns a list of uint16
-    numpy arrays."""
+def _decode_chunks(batch, model, codes, counts, idxs, raise_on_error, wide=False, hint=""):
+    """The four decode_chunks*: counts[k] symbols from codes[k], decoded with `batch` (idxs: None,
+    or one index array per chunk for its idx argument).  Returns uint8 (wide: uint16) arrays."""
     torch = _torch()
     dev = torch.device("cuda", model.ctx.device)
     n = len(codes)
@@ -1156,26 +801,146 @@ def decode_chunks_wide(model, codes, counts, raise_on_error=True):
     clen = np.array([len(c) for c in codes], dtype=np.int64)
     coff = np.zeros(n, dtype=np.int64)
     coff[1:] = np.cumsum(clen)[:-1]
-    counts = np.asarray(counts, dtype=np.int64)
-    if int(counts.max()) > N.MAX_CHUNK_SYMBOLS:
-        raise ChunkTooLongError(f"chunk of {int(counts.max())} symbols: the batch API takes at "
-                                f"most {N.MAX_CHUNK_SYMBOLS} per chunk")
-    sym_off = np.zeros(n + 1, dtype=np.int64)
-    sym_off[1:] = np.cumsum(counts)
+    sym_off = _offsets(np.asarray(counts, dtype=np.int64), hint)
     blob = np.frombuffer(b"".join(codes) + b"\0" * 16, dtype=np.uint8)
     code_d = torch.from_numpy(blob.copy()).to(dev)
-    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.int16, device=dev)
-    flags = decode_batch_wide(model, code_d, torch.from_numpy(coff).to(dev),
-                              torch.from_numpy(clen).to(dev), syms_d,
-                              torch.from_numpy(sym_off).to(dev))
+    side = () if idxs is None else (_to_dev(idxs, sym_off[-1], dev),)
+    syms_d = torch.empty(max(int(sym_off[-1]), 1), dtype=torch.int16 if wide else torch.uint8,
+                         device=dev)
+    flags = batch(model, code_d, torch.from_numpy(coff).to(dev), torch.from_numpy(clen).to(dev),
+                  *side, syms_d, torch.from_numpy(sym_off).to(dev))
     fl = flags.cpu().numpy()
-    host = syms_d.cpu().numpy().view(np.uint16)
-    res = []
-    for k in range(n):
-        if fl[k] and raise_on_error:
-            _raise_for_flag(int(fl[k]), f"chunk {k}")
-        res.append(host[sym_off[k]: sym_off[k + 1]].copy())
-    return res
+    host = syms_d.cpu().numpy()
+    if wide:
+        host = host.view(np.uint16)
+    if raise_on_error:
+        _raise_flagged(fl)
+    return [host[sym_off[k]: sym_off[k + 1]].copy() for k in range(n)]
+
+
+def encode_batch(model, syms, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch on torch tensors (async on torch's current stream).
+
+    syms uint8[...]; sym_off int64/uint64[n+1]; out uint8[...]; out_off int64/uint64[n+1].
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    return _encode_batch("rc_encode_batch", model, syms, None, sym_off, out, out_off, out_len,
+                         flags)
+
+
+def decode_batch(model, code, code_off, code_len, syms_out, sym_off, flags=None):
+    """rc_decode_batch on torch tensors (async on torch's current stream).  Returns flags."""
+    return _decode_batch("rc_decode_batch", model, code, code_off, code_len, None, syms_out,
+                         sym_off, flags)
+
+
+def encode_chunks(model, chunks, raise_on_error=True):
+    """Encode a list of symbol sequences (bytes / uint8 arrays), one chunk each.
+
+    Host-resident convenience: uploads, encodes on the GPU, re-encodes chunks that overflowed
+    their first slot with their exact length, downloads.  Returns a list of bytes."""
+    return _encode_chunks(encode_batch, model, [_u8_chunk(c) for c in chunks], None,
+                          raise_on_error, " (use Encoder for longer streams)")
+
+
+def decode_chunks(model, codes, counts, raise_on_error=True):
+    """Decode a list of code streams; counts[k] symbols each (the count is out-of-band,
+    as in the reference: sample_impl.rs:113-120).  Returns a list of uint8 numpy arrays."""
+    return _decode_chunks(decode_batch, model, codes, counts, None, raise_on_error,
+                          hint=" (use Decoder for longer streams)")
+
+
+# ------------------------------------------------------------- batch API, a model per symbol
+def encode_batch_indexed(model_set, syms, idx, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch_indexed on torch tensors (async on torch's current stream): encode_batch
+    with idx uint8[...], one row of model_set per symbol, indexed like syms.
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    return _encode_batch("rc_encode_batch_indexed", model_set, syms, idx, sym_off, out, out_off,
+                         out_len, flags)
+
+
+def decode_batch_indexed(model_set, code, code_off, code_len, idx, syms_out, sym_off, flags=None):
+    """rc_decode_batch_indexed on torch tensors (async on torch's current stream): decode_batch
+    with idx uint8[...], one row of model_set per symbol, indexed like syms_out.  Returns flags."""
+    return _decode_batch("rc_decode_batch_indexed", model_set, code, code_off, code_len, idx,
+                         syms_out, sym_off, flags)
+
+
+def encode_chunks_indexed(model_set, chunks, raise_on_error=True):
+    """encode_chunks over a list of (symbols, indexes) pairs (bytes / uint8 arrays of equal
+    length), one chunk each: symbol i is coded with row indexes[i].  Returns a list of bytes."""
+    pairs = [(_u8_chunk(s), _u8_chunk(x)) for s, x in chunks]
+    for k, (s, x) in enumerate(pairs):
+        if len(s) != len(x):
+            raise ValueError(f"chunk {k}: {len(s)} symbols, {len(x)} indexes")
+    return _encode_chunks(encode_batch_indexed, model_set, [s for s, _ in pairs],
+                          [x for _, x in pairs], raise_on_error)
+
+
+def decode_chunks_indexed(model_set, chunks, raise_on_error=True):
+    """decode_chunks over a list of (code, indexes) pairs: chunk k decodes len(indexes) symbols,
+    symbol i with row indexes[i].  Returns a list of uint8 numpy arrays."""
+    idxs = [_u8_chunk(x) for _, x in chunks]
+    return _decode_chunks(decode_batch_indexed, model_set, [c for c, _ in chunks],
+                          [len(x) for x in idxs], idxs, raise_on_error)
+
+
+# ------------------------------------------------- batch API, the previous symbol picks the model
+def encode_batch_order1(o1_set, syms, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch_order1 on torch tensors (async on torch's current stream): encode_batch
+    against an Order1ModelSet, the row of each symbol chosen by the chunk's previous symbol.
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    return _encode_batch("rc_encode_batch_order1", o1_set, syms, None, sym_off, out, out_off,
+                         out_len, flags)
+
+
+def decode_batch_order1(o1_set, code, code_off, code_len, syms_out, sym_off, flags=None):
+    """rc_decode_batch_order1 on torch tensors (async on torch's current stream): decode_batch
+    against an Order1ModelSet, the row of each symbol chosen by the previous decoded symbol.
+    Returns flags."""
+    return _decode_batch("rc_decode_batch_order1", o1_set, code, code_off, code_len, None,
+                         syms_out, sym_off, flags)
+
+
+def encode_chunks_order1(o1_set, chunks, raise_on_error=True):
+    """encode_chunks over a list of symbol chunks (bytes / uint8 arrays) against an
+    Order1ModelSet.  Returns a list of bytes."""
+    return _encode_chunks(encode_batch_order1, o1_set, [_u8_chunk(c) for c in chunks], None,
+                          raise_on_error)
+
+
+def decode_chunks_order1(o1_set, codes, counts, raise_on_error=True):
+    """decode_chunks against an Order1ModelSet: counts[k] symbols from codes[k] (the count is
+    out-of-band, as in the reference).  Returns a list of uint8 numpy arrays."""
+    return _decode_chunks(decode_batch_order1, o1_set, codes, counts, None, raise_on_error)
+
+
+# --------------------------------------------------------------- batch API, 16-bit symbols
+def encode_batch_wide(model, syms, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch_wide on torch tensors (async on torch's current stream): encode_batch with
+    syms uint16[...] (int16 is taken as uint16) against a WideStaticModel; sym_off counts symbols.
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    return _encode_batch("rc_encode_batch_wide", model, syms, None, sym_off, out, out_off,
+                         out_len, flags, wide=True)
+
+
+def decode_batch_wide(model, code, code_off, code_len, syms_out, sym_off, flags=None):
+    """rc_decode_batch_wide on torch tensors (async on torch's current stream): decode_batch into
+    syms_out uint16[...] (or int16, written as uint16).  Returns flags."""
+    return _decode_batch("rc_decode_batch_wide", model, code, code_off, code_len, None, syms_out,
+                         sym_off, flags, wide=True)
+
+
+def encode_chunks_wide(model, chunks, raise_on_error=True):
+    """encode_chunks over a list of 16-bit symbol sequences (uint16 arrays or lists of ints), one
+    chunk each, against a WideStaticModel.  Returns a list of bytes."""
+    return _encode_chunks(encode_batch_wide, model, [_u16_chunk(c) for c in chunks], None,
+                          raise_on_error)
+
+
+def decode_chunks_wide(model, codes, counts, raise_on_error=True):
+    """decode_chunks against a WideStaticModel; counts[k] symbols each.  Returns a list of uint16
+    numpy arrays."""
+    return _decode_chunks(decode_batch_wide, model, codes, counts, None, raise_on_error, wide=True)
 
 
 # ----------------------------------------------------------------------------- stream API

@@ -165,6 +165,9 @@ struct RcStamp {
 
 static __device__ __forceinline__ u32 hi32(u64 v) { return (u32)(v >> 32); }
 
+// (host) the bits of v: 0 for 0, else the position of its highest set bit plus one
+static inline u32 bitlen(u32 v) { return v ? 32u - (u32)__builtin_clz(v) : 0u; }
+
 // a - b (64-bit) with the borrow in an SGPR pair: the compiler's v_subb_co_u32_e32 reads VCC,
 // and a VALU read of VCC costs ~13 extra SIMD cycles on gfx950 (tools/ubench_issue.hip).
 // A VALU write of an SGPR read by a VALU as its carry-in needs 2 wait states on gfx950 (hipcc

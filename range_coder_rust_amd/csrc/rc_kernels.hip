@@ -144,8 +144,6 @@ struct DeviceGuard {
   }
 };
 
-u32 bitlen(u32 v) { return v ? 32u - (u32)__builtin_clz(v) : 0u; }
-
 thread_local char g_last_error[256] = "";
 
 rc_status device_error(hipError_t e, const char* what) {
@@ -247,6 +245,85 @@ static rc_status set_check(u32 n_models, u32 n_symbols, const u32* c, const u32*
     if (!table_ok(n_symbols, c + (size_t)j * n_symbols, cum + (size_t)j * n_symbols, total))
       return RC_E_BAD_MODEL;
   return RC_OK;
+}
+
+// A new model of `kind` on the context's device that owns one allocation holding the host
+// segments back to back (an empty one is skipped): every other field zero, div from the total.
+// *base: the allocation, segment i at the sum of the sizes before it.
+struct HostSeg {
+  const void* p;
+  size_t bytes;
+};
+static rc_status model_upload(rc_ctx* ctx, int kind, u32 total, std::initializer_list<HostSeg> segs,
+                              rc_model** out, char** base) {
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  size_t bytes = 0;
+  for (const HostSeg& sg : segs) bytes += sg.bytes;
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) return RC_E_DEVICE;
+  size_t at = 0;
+  for (const HostSeg& sg : segs) {
+    if (sg.bytes &&
+        hipMemcpy((char*)d + at, sg.p, sg.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipFree(d);
+      return RC_E_DEVICE;
+    }
+    at += sg.bytes;
+  }
+  rc_model* mm = new rc_model;
+  memset(mm, 0, sizeof *mm);
+  mm->kind = kind;
+  mm->device = ctx->device;
+  mm->div = (total & (total - 1)) == 0 ? DIV_POW2 : DIV_MAGIC;
+  mm->dmem = d;
+  *out = mm;
+  *base = (char*)d;
+  return RC_OK;
+}
+
+// the ModelArgs of the set, order-1 and wide kernels: the alphabet, the total's constants and the
+// decoder's buckets (the table pointers stay unused)
+static void small_model_args(ModelArgs& m, u32 n_symbols, u32 total, u32 bits, u32 shift) {
+  m.n = n_symbols;
+  m.ftotal = (float)total;
+  div_constants(m, total);
+  m.lut_bits = bits;
+  m.lut_shift = shift;
+}
+
+// The 8 words of a plan hook (rc_model_set_plan_, rc_model_order1_plan_, rc_model_wide_plan_):
+// encoder {lanes per workgroup, dynamic LDS bytes, table layout, table bytes}, decoder {lanes,
+// LDS bytes, log2 buckets per table, bucket shift}.
+template <class Plan, class F>
+static rc_status plan_hook(bool size_ok, u32 total, uint32_t* out, F plan) {
+  if (!out) return RC_E_ARG;
+  if (!size_ok || total < 256 || total > 65536) return RC_E_BAD_MODEL;
+  Plan p;
+  plan(&p);
+  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
+                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
+  memcpy(out, v, sizeof v);
+  return RC_OK;
+}
+
+// What every rc_{encode,decode}_batch* entry point does around its launch, in this order of
+// precedence: null context or model and too many chunks, a model of another kind (kinds: the
+// accepted ones as bits 1 << kind; kinds do not mix), a misaligned symbol pointer (the wide
+// calls' 16-bit symbols), the empty batch (RC_OK), a null array, a model of another device; then
+// the device, the stream service asked to yield, the launch and its error as `what`.
+template <class Launch>
+static rc_status batch_call(rc_ctx* ctx, const rc_model* m, u32 kinds, bool aligned,
+                            uint32_t n_chunks, bool arrays, const char* what, Launch launch) {
+  if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (!((kinds >> m->kind) & 1u) || !aligned) return RC_E_ARG;
+  if (n_chunks == 0) return RC_OK;
+  if (!arrays || m->device != ctx->device) return RC_E_ARG;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return RC_E_DEVICE;
+  rc_svc_yield_all_();
+  const hipError_t e = launch();
+  return e == hipSuccess ? RC_OK : device_error(e, what);
 }
 
 // range / total through the static coders' three range_par_total forms (rc_static.h), under
@@ -506,41 +583,22 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
     a.lut_max = (u32)lt.size() - 1;
     lut.swap(l8);
   }
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
   const size_t tab_bytes = 256 * sizeof(uint2);
   const size_t lut_bytes = lut.size() * sizeof(u32);
   const size_t pair_bytes = pair.size() * sizeof(u32);
-  void* d = nullptr;
-  if (hipMalloc(&d, tab_bytes + lut_bytes + pair_bytes) != hipSuccess) return RC_E_DEVICE;
-  if (hipMemcpy(d, tab.data(), tab_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)d + tab_bytes, lut.data(), lut_bytes, hipMemcpyHostToDevice) !=
-          hipSuccess ||
-      (pair_bytes && hipMemcpy((char*)d + tab_bytes + lut_bytes, pair.data(), pair_bytes,
-                               hipMemcpyHostToDevice) != hipSuccess)) {
-    (void)hipFree(d);
-    return RC_E_DEVICE;
-  }
+  rc_model* mm = nullptr;
+  char* d = nullptr;
+  const rc_status up = model_upload(
+      ctx, RC_KIND_STATIC, total_freq,
+      {{tab.data(), tab_bytes}, {lut.data(), lut_bytes}, {pair.data(), pair_bytes}}, &mm, &d);
+  if (up != RC_OK) return up;
   a.tab = (const uint2*)d;
-  a.lut = (const u32*)((char*)d + tab_bytes);
-  a.pair = pair_bytes ? (const u32*)((char*)d + tab_bytes + lut_bytes) : nullptr;
-  rc_model* mm = new rc_model;
-  mm->kind = 0;
-  mm->set = SetArgs{};
-  mm->plan = SetPlan{};
-  mm->wide = WideArgs{};
-  mm->wplan = WidePlan{};
-  mm->o1 = O1Args{};
-  mm->device = ctx->device;
-  mm->div = pow2 ? DIV_POW2 : DIV_MAGIC;
+  a.lut = (const u32*)(d + tab_bytes);
+  a.pair = pair_bytes ? (const u32*)(d + tab_bytes + lut_bytes) : nullptr;
   mm->args = a;
-  mm->dmem = d;
-  mm->ap = AdaptParams{};
-  memset(mm->c_host, 0, sizeof mm->c_host);
   for (u32 i = 0; i < n_symbols; ++i) mm->c_host[i] = c_freq[i];
   mm->complete = n_symbols == 256;
   for (u32 i = 0; i < n_symbols; ++i) mm->complete = mm->complete && c_freq[i] > 0;
-  mm->period = 0;
   *out = mm;
   return RC_OK;
 }
@@ -588,54 +646,40 @@ rc_status rc_model_destroy(rc_model* m) {
 rc_status rc_encode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
                           const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
                           const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
-  if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  // kinds do not mix: a static model set is coded by the indexed calls only, a wide model by
-  // the wide calls only
-  if (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE) return RC_E_ARG;
-  if (n_chunks == 0) return RC_OK;
-  if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
-  if (m->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  if (m->kind == 1) {
-    const hipError_t e = rc_adaptive_encode_launch(ctx->cur, m->ap, syms, sym_off, n_chunks,
-                                                   out, out_off, out_len, flags);
-    return e == hipSuccess ? RC_OK : device_error(e, "adaptive encode launch");
-  }
-  const bool sm = m->args.total >= 256 && m->args.total <= 65536;
-  const int smv = sm ? (m->complete ? 2 : 1) : 0;
-  const hipError_t e = rc_static_encode_launch(ctx->cur, ctx->knobs, m->args, m->div, smv, syms,
-                                               sym_off, n_chunks, out, out_off, out_len, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "encode launch");
+  // (a static model set is coded by the indexed calls only, a wide model by the wide calls only)
+  return batch_call(
+      ctx, m, 1u << RC_KIND_STATIC | 1u << RC_KIND_ADAPTIVE, true, n_chunks,
+      syms && sym_off && out && out_off && out_len && flags,
+      m && m->kind == RC_KIND_ADAPTIVE ? "adaptive encode launch" : "encode launch", [&] {
+        if (m->kind == RC_KIND_ADAPTIVE)
+          return rc_adaptive_encode_launch(ctx->cur, m->ap, syms, sym_off, n_chunks, out, out_off,
+                                           out_len, flags);
+        const bool sm = m->args.total >= 256 && m->args.total <= 65536;
+        const int smv = sm ? (m->complete ? 2 : 1) : 0;
+        return rc_static_encode_launch(ctx->cur, ctx->knobs, m->args, m->div, smv, syms, sym_off,
+                                       n_chunks, out, out_off, out_len, flags);
+      });
 }
 
 rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
                           const uint64_t* code_off, const uint64_t* code_len, uint8_t* syms_out,
                           const uint64_t* sym_off, uint32_t n_chunks, uint32_t* flags) {
-  if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  // kinds do not mix: a static model set is coded by the indexed calls only, a wide model by
-  // the wide calls only
-  if (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE) return RC_E_ARG;
-  if (n_chunks == 0) return RC_OK;
-  if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
-  if (m->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  if (m->kind == 1) {
-    const hipError_t e = rc_adaptive_decode_launch(ctx->cur, m->ap, code, code_off, code_len,
-                                                   syms_out, sym_off, n_chunks, flags);
-    return e == hipSuccess ? RC_OK : device_error(e, "adaptive decode launch");
-  }
-  const bool sm = m->args.total >= 256 && m->args.total <= 65536;
-  const hipError_t e =
-      m->div == DIV_POW2
-          ? rc_static_decode_launch_pow2(ctx->cur, ctx->knobs, m->args, sm, code, code_off, code_len,
-                                         syms_out, sym_off, n_chunks, flags)
-          : rc_static_decode_launch_magic(ctx->cur, ctx->knobs, m->args, sm, code, code_off, code_len,
-                                          syms_out, sym_off, n_chunks, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "decode launch");
+  return batch_call(
+      ctx, m, 1u << RC_KIND_STATIC | 1u << RC_KIND_ADAPTIVE, true, n_chunks,
+      code && code_off && code_len && syms_out && sym_off && flags,
+      m && m->kind == RC_KIND_ADAPTIVE ? "adaptive decode launch" : "decode launch", [&] {
+        if (m->kind == RC_KIND_ADAPTIVE)
+          return rc_adaptive_decode_launch(ctx->cur, m->ap, code, code_off, code_len, syms_out,
+                                           sym_off, n_chunks, flags);
+        const bool sm = m->args.total >= 256 && m->args.total <= 65536;
+        return m->div == DIV_POW2
+                   ? rc_static_decode_launch_pow2(ctx->cur, ctx->knobs, m->args, sm, code,
+                                                  code_off, code_len, syms_out, sym_off, n_chunks,
+                                                  flags)
+                   : rc_static_decode_launch_magic(ctx->cur, ctx->knobs, m->args, sm, code,
+                                                   code_off, code_len, syms_out, sym_off, n_chunks,
+                                                   flags);
+      });
 }
 
 // ---- static model sets (rc_indexed.h; kernels in rc_indexed.hip) ----
@@ -652,15 +696,8 @@ rc_status rc_model_set_check_(uint32_t n_models, uint32_t n_symbols, const uint3
 // entries, 1: cum-only rows), table bytes}, decoder {lanes, LDS bytes, log2 buckets per row,
 // bucket shift}.
 rc_status rc_model_set_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* out) {
-  if (!out) return RC_E_ARG;
-  if (n_models < 1 || n_models > RC_MAX_SET_MODELS || total_freq < 256 || total_freq > 65536)
-    return RC_E_BAD_MODEL;
-  SetPlan p;
-  rc_set_plan(n_models, total_freq, &p);
-  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
-                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
-  memcpy(out, v, sizeof v);
-  return RC_OK;
+  return plan_hook<SetPlan>(n_models >= 1 && n_models <= RC_MAX_SET_MODELS, total_freq, out,
+                            [&](SetPlan* p) { rc_set_plan(n_models, total_freq, p); });
 }
 
 // The device snapshot of a checked set for `plan` (rc_set_plan's, or rc_order1_plan's with
@@ -692,39 +729,22 @@ static rc_status set_build(rc_ctx* ctx, int kind, uint32_t n_models, uint32_t n_
       lut[(size_t)j * nb + b] = (e & 0xFFFFu) | (cum1 << 16);
     }
   }
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
   const size_t row_bytes = rows.size() * sizeof(u32), lut_bytes = lut.size() * sizeof(u32);
-  const size_t map_bytes = map256 ? 256 : 0;
-  void* d = nullptr;
-  if (hipMalloc(&d, row_bytes + lut_bytes + map_bytes) != hipSuccess) return RC_E_DEVICE;
-  if (hipMemcpy(d, rows.data(), row_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)d + row_bytes, lut.data(), lut_bytes, hipMemcpyHostToDevice) !=
-          hipSuccess ||
-      (map256 && hipMemcpy((char*)d + row_bytes + lut_bytes, map256, map_bytes,
-                           hipMemcpyHostToDevice) != hipSuccess)) {
-    (void)hipFree(d);
-    return RC_E_DEVICE;
-  }
-  rc_model* mm = new rc_model;
-  memset(mm, 0, sizeof *mm);
-  mm->kind = kind;
-  mm->device = ctx->device;
-  mm->div = (total_freq & (total_freq - 1)) == 0 ? DIV_POW2 : DIV_MAGIC;
-  mm->dmem = d;
+  rc_model* mm = nullptr;
+  char* d = nullptr;
+  const rc_status up = model_upload(
+      ctx, kind, total_freq,
+      {{rows.data(), row_bytes}, {lut.data(), lut_bytes}, {map256, map256 ? 256u : 0u}}, &mm, &d);
+  if (up != RC_OK) return up;
   mm->plan = plan;
   SetArgs& a = kind == RC_KIND_ORDER1 ? mm->o1.s : mm->set;
-  a.m.n = n_symbols;
-  a.m.ftotal = (float)total_freq;
-  div_constants(a.m, total_freq);
-  a.m.lut_bits = plan.dec_bits;
-  a.m.lut_shift = plan.dec_shift;
+  small_model_args(a.m, n_symbols, total_freq, plan.dec_bits, plan.dec_shift);
   a.rows = (const u32*)d;
-  a.lut = (const u32*)((char*)d + row_bytes);
+  a.lut = (const u32*)(d + row_bytes);
   a.k = n_models;
   a.tab_bytes = plan.enc_tab;
   if (kind == RC_KIND_ORDER1) {
-    mm->o1.map = (const uint8_t*)d + row_bytes + lut_bytes;
+    mm->o1.map = (const uint8_t*)(d + row_bytes + lut_bytes);
     mm->o1.first_row = first_row;
   }
   *out = mm;
@@ -748,36 +768,26 @@ rc_status rc_encode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_
                                   const uint8_t* idx, const uint64_t* sym_off,
                                   uint32_t n_chunks, uint8_t* out, const uint64_t* out_off,
                                   uint64_t* out_len, uint32_t* flags) {
-  if (!ctx || !set || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (set->kind != RC_KIND_SET) return RC_E_ARG;  // kinds do not mix
-  if (n_chunks == 0) return RC_OK;
-  if (!syms || !idx || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
-  if (set->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  const hipError_t e =
-      rc_set_encode_launch(ctx->cur, ctx->knobs, set->set, set->div, set->plan, syms, idx,
-                           sym_off, n_chunks, out, out_off, out_len, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "indexed encode launch");
+  return batch_call(ctx, set, 1u << RC_KIND_SET, true, n_chunks,
+                    syms && idx && sym_off && out && out_off && out_len && flags,
+                    "indexed encode launch", [&] {
+                      return rc_set_encode_launch(ctx->cur, ctx->knobs, set->set, set->div,
+                                                  set->plan, syms, idx, sym_off, n_chunks, out,
+                                                  out_off, out_len, flags);
+                    });
 }
 
 rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_t* code,
                                   const uint64_t* code_off, const uint64_t* code_len,
                                   const uint8_t* idx, uint8_t* syms_out, const uint64_t* sym_off,
                                   uint32_t n_chunks, uint32_t* flags) {
-  if (!ctx || !set || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (set->kind != RC_KIND_SET) return RC_E_ARG;  // kinds do not mix
-  if (n_chunks == 0) return RC_OK;
-  if (!code || !code_off || !code_len || !idx || !syms_out || !sym_off || !flags) return RC_E_ARG;
-  if (set->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  const hipError_t e =
-      rc_set_decode_launch(ctx->cur, ctx->knobs, set->set, set->div, set->plan, code, code_off,
-                           code_len, idx, syms_out, sym_off, n_chunks, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "indexed decode launch");
+  return batch_call(ctx, set, 1u << RC_KIND_SET, true, n_chunks,
+                    code && code_off && code_len && idx && syms_out && sym_off && flags,
+                    "indexed decode launch", [&] {
+                      return rc_set_decode_launch(ctx->cur, ctx->knobs, set->set, set->div,
+                                                  set->plan, code, code_off, code_len, idx,
+                                                  syms_out, sym_off, n_chunks, flags);
+                    });
 }
 
 // ---- order-1 sets (rc_order1.h; kernels in rc_order1.hip) ----
@@ -804,15 +814,8 @@ rc_status rc_model_order1_check_(uint32_t n_models, uint32_t n_symbols, const ui
 // rc_model_order1_plan_: rc_model_set_plan_ for an order-1 set (the decoder's LDS includes the
 // map; the encoder's numbers are the set's).
 rc_status rc_model_order1_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* out) {
-  if (!out) return RC_E_ARG;
-  if (n_models < 1 || n_models > RC_MAX_SET_MODELS || total_freq < 256 || total_freq > 65536)
-    return RC_E_BAD_MODEL;
-  SetPlan p;
-  rc_order1_plan(n_models, total_freq, &p);
-  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
-                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
-  memcpy(out, v, sizeof v);
-  return RC_OK;
+  return plan_hook<SetPlan>(n_models >= 1 && n_models <= RC_MAX_SET_MODELS, total_freq, out,
+                            [&](SetPlan* p) { rc_order1_plan(n_models, total_freq, p); });
 }
 
 rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
@@ -836,36 +839,26 @@ rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_
 rc_status rc_encode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,
                                  const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
                                  const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
-  if (!ctx || !o1 || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (o1->kind != RC_KIND_ORDER1) return RC_E_ARG;  // kinds do not mix
-  if (n_chunks == 0) return RC_OK;
-  if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
-  if (o1->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  const hipError_t e =
-      rc_order1_encode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div, o1->plan, syms, sym_off,
-                              n_chunks, out, out_off, out_len, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "order-1 encode launch");
+  return batch_call(ctx, o1, 1u << RC_KIND_ORDER1, true, n_chunks,
+                    syms && sym_off && out && out_off && out_len && flags,
+                    "order-1 encode launch", [&] {
+                      return rc_order1_encode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div,
+                                                     o1->plan, syms, sym_off, n_chunks, out,
+                                                     out_off, out_len, flags);
+                    });
 }
 
 rc_status rc_decode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* code,
                                  const uint64_t* code_off, const uint64_t* code_len,
                                  uint8_t* syms_out, const uint64_t* sym_off, uint32_t n_chunks,
                                  uint32_t* flags) {
-  if (!ctx || !o1 || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (o1->kind != RC_KIND_ORDER1) return RC_E_ARG;  // kinds do not mix
-  if (n_chunks == 0) return RC_OK;
-  if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
-  if (o1->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  const hipError_t e =
-      rc_order1_decode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div, o1->plan, code, code_off,
-                              code_len, syms_out, sym_off, n_chunks, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "order-1 decode launch");
+  return batch_call(ctx, o1, 1u << RC_KIND_ORDER1, true, n_chunks,
+                    code && code_off && code_len && syms_out && sym_off && flags,
+                    "order-1 decode launch", [&] {
+                      return rc_order1_decode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div,
+                                                     o1->plan, code, code_off, code_len, syms_out,
+                                                     sym_off, n_chunks, flags);
+                    });
 }
 
 // rc_encode_host / rc_decode_host: the pipelined host path lives in rc_stream.hip
@@ -980,15 +973,8 @@ rc_status rc_model_wide_check_(uint32_t n_symbols, const uint32_t* c_freq,
 // out[8] = encoder {lanes per workgroup, dynamic LDS bytes, table layout (0: 8-B (cum, c)
 // entries, 1: cum-only row), table bytes}, decoder {lanes, LDS bytes, log2 buckets, bucket shift}.
 rc_status rc_model_wide_plan_(uint32_t n_symbols, uint32_t total_freq, uint32_t* out) {
-  if (!out) return RC_E_ARG;
-  if (n_symbols < 1 || n_symbols > RC_MAX_WIDE_SYMBOLS || total_freq < 256 || total_freq > 65536)
-    return RC_E_BAD_MODEL;
-  WidePlan p;
-  rc_wide_plan(n_symbols, total_freq, &p);
-  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
-                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
-  memcpy(out, v, sizeof v);
-  return RC_OK;
+  return plan_hook<WidePlan>(n_symbols >= 1 && n_symbols <= RC_MAX_WIDE_SYMBOLS, total_freq, out,
+                             [&](WidePlan* p) { rc_wide_plan(n_symbols, total_freq, p); });
 }
 
 rc_status rc_model_create_static_wide(rc_ctx* ctx, uint32_t n_symbols, const uint32_t* c_freq,
@@ -1009,32 +995,17 @@ rc_status rc_model_create_static_wide(rc_ctx* ctx, uint32_t n_symbols, const uin
   const std::vector<u32> lut =
       wide_buckets(n_symbols, cum_freq, total_freq, plan.dec_bits, plan.dec_shift,
                    &top_stride);
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
   const size_t row_bytes = row.size() * sizeof(u32), lut_bytes = lut.size() * sizeof(u32);
-  void* d = nullptr;
-  if (hipMalloc(&d, row_bytes + lut_bytes) != hipSuccess) return RC_E_DEVICE;
-  if (hipMemcpy(d, row.data(), row_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)d + row_bytes, lut.data(), lut_bytes, hipMemcpyHostToDevice) !=
-          hipSuccess) {
-    (void)hipFree(d);
-    return RC_E_DEVICE;
-  }
-  rc_model* mm = new rc_model;
-  memset(mm, 0, sizeof *mm);
-  mm->kind = RC_KIND_WIDE;
-  mm->device = ctx->device;
-  mm->div = (total_freq & (total_freq - 1)) == 0 ? DIV_POW2 : DIV_MAGIC;
-  mm->dmem = d;
+  rc_model* mm = nullptr;
+  char* d = nullptr;
+  const rc_status up = model_upload(ctx, RC_KIND_WIDE, total_freq,
+                                    {{row.data(), row_bytes}, {lut.data(), lut_bytes}}, &mm, &d);
+  if (up != RC_OK) return up;
   mm->wplan = plan;
   WideArgs& a = mm->wide;
-  a.m.n = n_symbols;
-  a.m.ftotal = (float)total_freq;
-  div_constants(a.m, total_freq);
-  a.m.lut_bits = plan.dec_bits;
-  a.m.lut_shift = plan.dec_shift;
+  small_model_args(a.m, n_symbols, total_freq, plan.dec_bits, plan.dec_shift);
   a.row = (const u32*)d;
-  a.lut = (const u32*)((char*)d + row_bytes);
+  a.lut = (const u32*)(d + row_bytes);
   a.top_stride = top_stride;
   a.tab_bytes = plan.enc_tab;
   *out = mm;
@@ -1044,38 +1015,26 @@ rc_status rc_model_create_static_wide(rc_ctx* ctx, uint32_t n_symbols, const uin
 rc_status rc_encode_batch_wide(rc_ctx* ctx, const rc_model* wide, const void* syms,
                                const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
                                const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
-  if (!ctx || !wide || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (wide->kind != RC_KIND_WIDE) return RC_E_ARG;  // kinds do not mix
-  if (((uintptr_t)syms & 1u) != 0) return RC_E_ARG;  // 16-bit symbols
-  if (n_chunks == 0) return RC_OK;
-  if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
-  if (wide->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  const hipError_t e =
-      rc_wide_encode_launch(ctx->cur, ctx->knobs, wide->wide, wide->div, wide->wplan,
-                            (const uint16_t*)syms, sym_off, n_chunks, out, out_off, out_len, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "wide encode launch");
+  return batch_call(ctx, wide, 1u << RC_KIND_WIDE, ((uintptr_t)syms & 1u) == 0, n_chunks,
+                    syms && sym_off && out && out_off && out_len && flags, "wide encode launch",
+                    [&] {
+                      return rc_wide_encode_launch(ctx->cur, ctx->knobs, wide->wide, wide->div,
+                                                   wide->wplan, (const uint16_t*)syms, sym_off,
+                                                   n_chunks, out, out_off, out_len, flags);
+                    });
 }
 
 rc_status rc_decode_batch_wide(rc_ctx* ctx, const rc_model* wide, const uint8_t* code,
                                const uint64_t* code_off, const uint64_t* code_len,
                                void* syms_out, const uint64_t* sym_off, uint32_t n_chunks,
                                uint32_t* flags) {
-  if (!ctx || !wide || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (wide->kind != RC_KIND_WIDE) return RC_E_ARG;  // kinds do not mix
-  if (((uintptr_t)syms_out & 1u) != 0) return RC_E_ARG;  // 16-bit symbols
-  if (n_chunks == 0) return RC_OK;
-  if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
-  if (wide->device != ctx->device) return RC_E_ARG;
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return RC_E_DEVICE;
-  rc_svc_yield_all_();
-  const hipError_t e =
-      rc_wide_decode_launch(ctx->cur, ctx->knobs, wide->wide, wide->div, wide->wplan, code,
-                            code_off, code_len, (uint16_t*)syms_out, sym_off, n_chunks, flags);
-  return e == hipSuccess ? RC_OK : device_error(e, "wide decode launch");
+  return batch_call(ctx, wide, 1u << RC_KIND_WIDE, ((uintptr_t)syms_out & 1u) == 0, n_chunks,
+                    code && code_off && code_len && syms_out && sym_off && flags,
+                    "wide decode launch", [&] {
+                      return rc_wide_decode_launch(ctx->cur, ctx->knobs, wide->wide, wide->div,
+                                                   wide->wplan, code, code_off, code_len,
+                                                   (uint16_t*)syms_out, sym_off, n_chunks, flags);
+                    });
 }
 
 }  // extern "C"

@@ -11,8 +11,7 @@
 
 #include "rc_encode.inc"
 #include "rc_decode.inc"
-
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+#include "rc_cuwg.inc"
 
 // dummy symbol tiles of dead lanes (zeros)
 __device__ uint4 g_o1sink[4];
@@ -25,20 +24,6 @@ __device__ uint4 g_o1sink[4];
 template <int LAYOUT>
 static __device__ __forceinline__ u32 o1_row_bytes() {
   return LAYOUT == 0 ? 2048u : 4u * SET_ROW_WORDS;
-}
-
-// the (cum, c) entry of symbol s in the row at LDS byte offset ro, in enc_core's SM 1 form (as
-// set_entry of rc_indexed.hip, without the clamp to a poison row: ro comes from the staged map)
-template <int LAYOUT>
-static __device__ __forceinline__ uint2 o1_row_entry(u32 ro, u32 s) {
-  if (LAYOUT == 0) {
-    const u32x2 v = *(const __attribute__((address_space(3))) u32x2*)(uintptr_t)(ro + (s << 3));
-    return make_uint2(v.x, v.y);
-  }
-  const l_u32* rp = (const l_u32*)(uintptr_t)(ro + (s << 2));
-  const u32 c0 = rp[0], c1 = rp[1];
-  const u32 c = c1 - c0;
-  return make_uint2(c0 | ((c - 1u) & 0xFF000000u), max(c, 1u));
 }
 
 // the row offset the map gives for previous symbol p (a byte: every one of the 256 staged
@@ -65,15 +50,15 @@ static __device__ __forceinline__ void o1_enc16(Enc& e, const ModelArgs& m, u32 
   r[0] = ro;
 #pragma unroll
   for (int j = 1; j <= 16; ++j) r[j] = o1_map(map_off, O1_SYM(j - 1));
-  uint2 t = o1_row_entry<LAYOUT>(r[0], O1_SYM(0));
+  uint2 t = cuwg_enc_entry<LAYOUT>(r[0], O1_SYM(0));
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
 #pragma unroll
     for (int i = 0; i < 4; i += 2) {
       const int j = 4 * q + i;
-      const uint2 t1 = o1_row_entry<LAYOUT>(r[j + 1], O1_SYM(j + 1));
+      const uint2 t1 = cuwg_enc_entry<LAYOUT>(r[j + 1], O1_SYM(j + 1));
       // (past the tile's end: a harmless read of the last symbol in the next row)
-      const uint2 tn = o1_row_entry<LAYOUT>(r[j + 2], O1_SYM(j + 2 < 16 ? j + 2 : 15));
+      const uint2 tn = cuwg_enc_entry<LAYOUT>(r[j + 2], O1_SYM(j + 2 < 16 ? j + 2 : 15));
       enc_sym2<DIV, 1>(e, m, t, t1, act, lane, wring, wout, wrank);
       t = tn;
     }
@@ -90,7 +75,7 @@ static __device__ __forceinline__ void o1_enc_byte(Enc& e, const ModelArgs& m, u
                                                    u32 lane, const u32* wring, const EncOut* wout,
                                                    u32* wrank) {
   const u32 sym = act ? (u32)sp[i] : 0u;
-  enc_sym<DIV, 1>(e, m, o1_row_entry<LAYOUT>(ro, sym), act, lane, wring, wout, wrank);
+  enc_sym<DIV, 1>(e, m, cuwg_enc_entry<LAYOUT>(ro, sym), act, lane, wring, wout, wrank);
   const u32 rn = o1_map(map_off, sym);
   if (act) ro = rn;
 }
@@ -138,52 +123,25 @@ __global__ __launch_bounds__(1024) void k_encode_order1(
   }
   for (u32 p = tid; p < 256u; p += lanes)
     s_enc[map_off / 4 + p] = (u32)oa.map[p] * o1_row_bytes<LAYOUT>();
-  const u32 nw = lanes >> 6;
-  u32* const s_ring = s_enc + a.tab_bytes / 4;
-  EncOut* const s_out = reinterpret_cast<EncOut*>(s_ring + nw * ENC_RING * 64);
-  u32* const s_rank = reinterpret_cast<u32*>(s_out + lanes);
+  const CuwgEncLds l = cuwg_enc_lds(s_enc, a.tab_bytes, lanes);
   const u32 lane = tid & 63, wave = tid >> 6;
   const u32 k = blockIdx.x * lanes + tid;
   const bool live = k < n_chunks;  // dead lanes still take part in the wave's flush rounds
   RC_VGPR_FLOOR_128();
 
-  u64 s0 = 0, n = 0, o0 = 0, o1 = 0;
-  if (live) {
-    s0 = sym_off[k];
-    n = sym_off[k + 1] - s0;
-    o0 = out_off[k];
-    o1 = out_off[k + 1];
-  }
-  // B (bit position) is 32-bit: a longer chunk is flagged, not read, and its slot not written
-  const bool too_long = n > RC_MAX_CHUNK_SYMBOLS;
-  if (too_long) {
-    n = 0;
-    o1 = o0;
-  }
-  const u32 al = (u32)(((uintptr_t)out + o0) & (ENC_UNIT - 1));
-  u64 cap = o1 - o0;
-  if (cap > 0xFFFFFF00ull - al) cap = 0xFFFFFF00ull - al;
-  s_out[tid].gbase = out + o0 - al;
-  s_out[tid].lo_ok = al;
-  s_out[tid].hi_ok = al + (u32)cap;
+  const CuwgChunk ch = cuwg_enc_begin(&l.out[tid], out, sym_off, out_off, k, live);
   __syncthreads();
-  const u32* wring = s_ring + wave * ENC_RING * 64;
-  const EncOut* wout = s_out + wave * 64;
-  u32* const wrank = s_rank + wave * 64;
+  const u32* wring = l.ring + wave * ENC_RING * 64;
+  const EncOut* wout = l.out + wave * 64;
+  u32* const wrank = l.rank + wave * 64;
 
   Enc e;
-  e.low = 0;  // RangeCoder::default (range_coder.rs:13-20)
-  e.range = ~0ull;
-  e.acc = 0;
-  e.B = 8 * al;  // pad bytes in front of the slot (never stored)
-  e.fthr = 8u * FLUSH_AT;  // fpos = 0
-  e.err = 0;
-  e.ring = a.tab_bytes + 4u * (wave * ENC_RING * 64 + ring_col(lane));
+  cuwg_enc_init(e, ch.al, a.tab_bytes, wave, lane);
 
-  const uint8_t* sp = syms + s0;
+  const uint8_t* sp = syms + ch.s0;
   u32 ro = oa.first_row * o1_row_bytes<LAYOUT>();  // the row of the lane's next symbol
   // (n <= 2^25 here: the symbol counters are 32-bit, which keeps the tile registers free)
-  const u32 nn = (u32)n;
+  const u32 nn = (u32)ch.n;
   u32 head = (64 - ((u32)(uintptr_t)sp & 63)) & 63;  // symbols before the first 64-B aligned tile
   if (head > nn) head = nn;
   const u32 ntile = (nn - head) >> 6;
@@ -194,11 +152,7 @@ __global__ __launch_bounds__(1024) void k_encode_order1(
   }
   // body, part 1: the tiles every live lane of the wave has, with every lane active; dead lanes
   // run along on a dummy tile and a slot with no writable bytes
-  u32 tm = live ? ntile : ~0u;
-#pragma unroll
-  for (int o = 32; o; o >>= 1) tm = min(tm, (u32)__shfl_xor((int)tm, o));
-  if (tm == ~0u) tm = 0;  // no live lane in this wave
-  const u32 tmin = __builtin_amdgcn_readfirstlane(tm);  // wave-uniform (scalar) trip count
+  const u32 tmin = cuwg_tmin(live, ntile);
   const uint8_t* tp = live ? sp + head : reinterpret_cast<const uint8_t*>(g_o1sink);
   // 64-symbol tiles, 4 x 16 B per lane, the next tile in flight while the current one is coded
   // (explicit registers, as in k_encode_static)
@@ -246,66 +200,18 @@ __global__ __launch_bounds__(1024) void k_encode_order1(
     if ((j & 7) == 7) enc_flush(e, lane, wring, wout, wrank);
   }
 
-  // Encoder::finish (encoder.rs:40-46): 8 x left_shift
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    enc_emit_byte(e, (u32)(e.low >> 56));
-    e.low <<= 8;
-  }
-  const u32 len = (e.B >> 3) - al;
-  u32 wend = enc_wpos(e);
-  if (e.B & 31) {  // the last, incomplete dword
-    ring_put(e.ring, (e.B >> 5) & (ENC_RING - 1), (u32)(e.acc << (32 - (e.B & 31))));
-    wend += 4;
-  }
-  // final rounds: the last (partial) units, clipped to the stream end
-  const u32 end = al + len;
-  if (end < s_out[tid].hi_ok) s_out[tid].hi_ok = end;
-  while (__any((int)(enc_fpos(e) < wend)))
-    enc_round(e, enc_fpos(e) < wend, lane, wring, wout, wrank);
-  if (live) {
-    e.err = (e.err >> 24) ? o1_first_error(a.rows, oa.map, oa.first_row, m.n, sp, n) : 0u;
-    if (!e.err && (u64)len > cap) e.err = RC_F_CAPACITY;
-    out_len[k] = too_long ? 0u : len;
-    flags[k] = too_long ? RC_F_TOO_LONG : e.err;
-  }
+  const u32 len = cuwg_enc_finish(e, &l.out[tid], ch.al, lane, wring, wout, wrank);
+  if (live)
+    cuwg_enc_report(ch, k, len,
+                    (e.err >> 24) ? o1_first_error(a.rows, oa.map, oa.first_row, m.n, sp, ch.n)
+                                  : 0u,
+                    out_len, flags);
 }
 
 // ------------------------------------------------------------------------------------------
 // Decoder
 // ------------------------------------------------------------------------------------------
 typedef Dec<DEC_LD, 0> O1Dec;
-
-// (cum, c) of symbol s from the cum-only row at LDS byte address rowa (set_row_entry and
-// set_dec_fix are file-local to rc_indexed.hip; restated here, as §9.5 restated dec_fix, so that
-// no existing kernel's code depends on this file)
-static __device__ __forceinline__ uint2 o1_cum_entry(u32 rowa, u32 s) {
-  const l_u32* rp = (const l_u32*)(uintptr_t)(rowa + (s << 2));
-  const u32 c0 = rp[0], c1 = rp[1];
-  return make_uint2(c0, c1 - c0);
-}
-
-// the exact index s = #{ j in [1, n-1] : r * cum[j] <= x } (FreqTable::find_index) over a
-// cum-only row, walked from the candidate
-static __device__ __forceinline__ void o1_dec_fix(u32& s, uint2& t, u64& A, u64& B, u64 x, u64 r,
-                                                  u32 rowa, u32 n) {
-  s &= 255u;
-  if (A > x) {
-    do {
-      --s;
-      t = o1_cum_entry(rowa, s);
-      A = r * (u64)t.x;
-    } while (A > x);
-    B = r * (u64)t.y;
-  } else {
-    while (s + 1 < n && x - A >= B) {
-      ++s;
-      t = o1_cum_entry(rowa, s);
-      A = r * (u64)t.x;
-      B = r * (u64)t.y;
-    }
-  }
-}
 
 // the decoder's map word of row j: (LDS byte address of the cum row >> 2) | (the row's first
 // bucket, in words) << 16; both are below 40,960 (160 KiB of 4-B words)
@@ -335,7 +241,7 @@ static __device__ __forceinline__ u32 o1_dec_sym(O1Dec& d, const ModelArgs& m, u
   const u32 below = smask((qh & 0xFFFFu) - (ent >> 16));
   u32 s = __builtin_amdgcn_ubfe(ent, mselc(below, 0u, 8u), 8);
   const u32 rowa = (cw & 0xFFFFu) << 2;
-  uint2 t = o1_cum_entry(rowa, s);
+  uint2 t = cuwg_cum_entry(rowa, s);
   u32 nw = *(const l_u32*)(uintptr_t)(map_off + (s << 2));  // (s < 256: inside the staged map)
   float tc = m.ftotal * __builtin_amdgcn_rcpf(cvt_f32(t.y));  // (hint only)
   u64 B = mul_rv<1>(r, t.y);
@@ -343,7 +249,7 @@ static __device__ __forceinline__ u32 o1_dec_sym(O1Dec& d, const ModelArgs& m, u
   const u64 dx = sub64((u32)d.dat, d.dhi(), d.low + A);  // x - r cum
   if (__builtin_expect(__any((int)(dx >= B)), 0)) {
     if (dx >= B) {
-      o1_dec_fix(s, t, A, B, d.x(), r, rowa, m.n);
+      cuwg_dec_fix<true>(s, t, A, B, d.x(), r, rowa, m.n);
       nw = *(const l_u32*)(uintptr_t)(map_off + (s << 2));
       tc = m.ftotal * __builtin_amdgcn_rcpf(cvt_f32(t.y));
       // the buckets only hold symbols with c > 0, so c == 0 can only come from the fix-up: corrupt
@@ -497,50 +403,19 @@ __global__ __launch_bounds__(1024) void k_decode_order1(
     op[i] = (uint8_t)o1_dec_sym<DIV>(d, m, map_off, cw);
     dec_check4<1>(d);
   }
-  // shift_left_buffer panics once more bytes are needed than the stream holds (decoder.rs:33)
-  if (!d.err && d.bpos > d.limb) d.err = RC_F_TRUNCATED;
-  flags[k] = d.err;
+  flags[k] = cuwg_dec_flag(d);
 }
 
 // ------------------------------------------------------------------------------------------
 // Host: the plan and the launchers
 // ------------------------------------------------------------------------------------------
-static u32 o1_bitlen(u32 v) { return v ? 32u - (u32)__builtin_clz(v) : 0u; }
-
 void rc_order1_plan(u32 K, u32 total, SetPlan* p) {
   // encoder: the set's plan as it is (the map takes the place of the poison row K, which both
   // layouts reserve at least O1_MAP_BYTES for)
   rc_set_plan(K, total, p);
   if (!p->enc_lanes) return;
   // decoder: rc_set_plan's rule with the map counted beside the rows
-  const u32 bl = o1_bitlen(total - 1);
-  const u32 cap = bl < 12u ? bl : 12u;
-  const u32 tables = K * 4u * SET_ROW_WORDS + O1_MAP_BYTES;
-  auto bits_at = [&](u32 lanes) -> int {
-    const u32 fixed = tables + lanes * SET_DEC_LANE_BYTES;
-    int b = -1;
-    for (u32 t = 0; t <= cap; ++t)
-      if (fixed + K * (4u << t) <= SET_LDS_BYTES) b = (int)t;
-    return b;
-  };
-  u32 best_lanes = 0;
-  int best = -1;
-  for (u32 lanes = 1024; lanes >= 512; lanes -= 256) {
-    const int b = bits_at(lanes);
-    if (b >= (int)(cap < 8u ? cap : 8u)) {
-      best_lanes = lanes;
-      best = b;
-      break;
-    }
-    if (b > best) {
-      best_lanes = lanes;
-      best = b;
-    }
-  }
-  p->dec_lanes = best_lanes;
-  p->dec_bits = (u32)best;
-  p->dec_shift = bl > p->dec_bits ? bl - p->dec_bits : 0u;
-  p->dec_lds = tables + K * (4u << p->dec_bits) + best_lanes * SET_DEC_LANE_BYTES;
+  cuwg_dec_plan(p, total, K * 4u * SET_ROW_WORDS + O1_MAP_BYTES, K, 8u);
 }
 
 hipError_t rc_order1_encode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a_in,
@@ -549,25 +424,13 @@ hipError_t rc_order1_encode_launch(hipStream_t stream, const RcKnobs& k, const O
                                    const u64* out_off, u64* out_len, u32* flags) {
   O1Args a = a_in;
   a.s.tab_bytes = p.enc_tab;
-  hipError_t lds_err = hipSuccess;
-  const u32 lanes = set_launch_lanes(p.enc_lanes, n_chunks);
-  const u32 lds = p.enc_tab + lanes * SET_ENC_LANE_BYTES;
-  const dim3 grid((n_chunks + lanes - 1) / lanes), block(lanes);
   auto go = [&](auto kern) {
-    if ((lds_err = set_allow_lds(reinterpret_cast<const void*>(kern))) != hipSuccess) return;
-    rc_prio_policy(a.s.m, kPrioEncoder, grid.x,
-                   rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)lanes, lds), k);
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a, syms, sym_off, n_chunks, out, out_off,
-                       out_len, flags);
+    return cuwg_launch(kern, stream, k, a, a.s.m, kPrioEncoder, p.enc_lanes, SET_ENC_LANE_BYTES,
+                       p.enc_lds, n_chunks, syms, sym_off, n_chunks, out, out_off, out_len, flags);
   };
-  if (div == DIV_POW2) {
-    if (p.enc_layout == 0) go(k_encode_order1<DIV_POW2, 0>);
-    else go(k_encode_order1<DIV_POW2, 1>);
-  } else {
-    if (p.enc_layout == 0) go(k_encode_order1<DIV_MAGIC, 0>);
-    else go(k_encode_order1<DIV_MAGIC, 1>);
-  }
-  return lds_err != hipSuccess ? lds_err : hipGetLastError();
+  if (div == DIV_POW2)
+    return p.enc_layout == 0 ? go(k_encode_order1<DIV_POW2, 0>) : go(k_encode_order1<DIV_POW2, 1>);
+  return p.enc_layout == 0 ? go(k_encode_order1<DIV_MAGIC, 0>) : go(k_encode_order1<DIV_MAGIC, 1>);
 }
 
 hipError_t rc_order1_decode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a_in,
@@ -575,18 +438,10 @@ hipError_t rc_order1_decode_launch(hipStream_t stream, const RcKnobs& k, const O
                                    const u64* code_off, const u64* code_len, uint8_t* syms_out,
                                    const u64* sym_off, u32 n_chunks, u32* flags) {
   O1Args a = a_in;
-  hipError_t lds_err = hipSuccess;
-  const u32 lanes = set_launch_lanes(p.dec_lanes, n_chunks);
-  const u32 lds = p.dec_lds - (p.dec_lanes - lanes) * SET_DEC_LANE_BYTES;
-  const dim3 grid((n_chunks + lanes - 1) / lanes), block(lanes);
   auto go = [&](auto kern) {
-    if ((lds_err = set_allow_lds(reinterpret_cast<const void*>(kern))) != hipSuccess) return;
-    rc_prio_policy(a.s.m, kPrioDecoder512, grid.x,
-                   rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)lanes, lds), k);
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a, code, code_off, code_len, syms_out,
+    return cuwg_launch(kern, stream, k, a, a.s.m, kPrioDecoder512, p.dec_lanes,
+                       SET_DEC_LANE_BYTES, p.dec_lds, n_chunks, code, code_off, code_len, syms_out,
                        sym_off, n_chunks, flags);
   };
-  if (div == DIV_POW2) go(k_decode_order1<DIV_POW2>);
-  else go(k_decode_order1<DIV_MAGIC>);
-  return lds_err != hipSuccess ? lds_err : hipGetLastError();
+  return div == DIV_POW2 ? go(k_decode_order1<DIV_POW2>) : go(k_decode_order1<DIV_MAGIC>);
 }

@@ -10,8 +10,7 @@
 
 #include "rc_encode.inc"
 #include "rc_decode.inc"
-
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
+#include "rc_cuwg.inc"
 
 // dummy symbol tile of dead lanes (zeros: symbol 0 is in every alphabet)
 __device__ uint4 g_wsink[4];
@@ -20,22 +19,12 @@ __device__ uint4 g_wsink[4];
 // Encoder
 // ------------------------------------------------------------------------------------------
 
-// the (cum, c) entry of symbol s, in enc_core's SM 1 form: a symbol the reference cannot encode
-// carries a flag byte above its cum and c = 1.  A symbol >= n reads entry n.  Layout 0: the 8-B
-// entry as staged (entry n the poison entry), one ds_read_b64.  Layout 1: the cum-only row,
-// c = cum[s + 1] - cum[s] (one ds_read2_b32); c = 0 covers zero frequencies and symbols past the
-// alphabet (cum[n] = cum[n + 1] = total) alike.
+// the (cum, c) entry of symbol s (cuwg_enc_entry of the one table at LDS address 0).  A symbol
+// >= n reads entry n: the poison entry (layout 0), or cum[n] = cum[n + 1] = total, so c = 0
+// (layout 1).
 template <int LAYOUT>
 static __device__ __forceinline__ uint2 wide_entry(u32 n, u32 s) {
-  const u32 sc = min(s, n);
-  if (LAYOUT == 0) {
-    const u32x2 v = *(const __attribute__((address_space(3))) u32x2*)(uintptr_t)(sc << 3);
-    return make_uint2(v.x, v.y);
-  }
-  const l_u32* rp = (const l_u32*)(uintptr_t)(sc << 2);
-  const u32 c0 = rp[0], c1 = rp[1];
-  const u32 c = c1 - c0;
-  return make_uint2(c0 | ((c - 1u) & 0xFF000000u), max(c, 1u));
+  return cuwg_enc_entry<LAYOUT>(0u, min(s, n));
 }
 
 // 8 symbols from one 16-B load, as enc16's quarters: the table entry is read two symbols ahead,
@@ -102,51 +91,24 @@ __global__ __launch_bounds__(1024) void k_encode_wide(
   } else {
     for (u32 s = tid; s < m.n + 2; s += lanes) s_enc[s] = a.row[s];
   }
-  const u32 nw = lanes >> 6;
-  u32* const s_ring = s_enc + a.tab_bytes / 4;
-  EncOut* const s_out = reinterpret_cast<EncOut*>(s_ring + nw * ENC_RING * 64);
-  u32* const s_rank = reinterpret_cast<u32*>(s_out + lanes);
+  const CuwgEncLds l = cuwg_enc_lds(s_enc, a.tab_bytes, lanes);
   const u32 lane = tid & 63, wave = tid >> 6;
   const u32 k = blockIdx.x * lanes + tid;
   const bool live = k < n_chunks;  // dead lanes still take part in the wave's flush rounds
   RC_VGPR_FLOOR_128();
 
-  u64 s0 = 0, n = 0, o0 = 0, o1 = 0;
-  if (live) {
-    s0 = sym_off[k];
-    n = sym_off[k + 1] - s0;
-    o0 = out_off[k];
-    o1 = out_off[k + 1];
-  }
-  // B (bit position) is 32-bit: a longer chunk is flagged, not read, and its slot not written
-  const bool too_long = n > RC_MAX_CHUNK_SYMBOLS;
-  if (too_long) {
-    n = 0;
-    o1 = o0;
-  }
-  const u32 al = (u32)(((uintptr_t)out + o0) & (ENC_UNIT - 1));
-  u64 cap = o1 - o0;
-  if (cap > 0xFFFFFF00ull - al) cap = 0xFFFFFF00ull - al;
-  s_out[tid].gbase = out + o0 - al;
-  s_out[tid].lo_ok = al;
-  s_out[tid].hi_ok = al + (u32)cap;
+  const CuwgChunk ch = cuwg_enc_begin(&l.out[tid], out, sym_off, out_off, k, live);
   __syncthreads();
-  const u32* wring = s_ring + wave * ENC_RING * 64;
-  const EncOut* wout = s_out + wave * 64;
-  u32* const wrank = s_rank + wave * 64;
+  const u32* wring = l.ring + wave * ENC_RING * 64;
+  const EncOut* wout = l.out + wave * 64;
+  u32* const wrank = l.rank + wave * 64;
 
   Enc e;
-  e.low = 0;  // RangeCoder::default (range_coder.rs:13-20)
-  e.range = ~0ull;
-  e.acc = 0;
-  e.B = 8 * al;  // pad bytes in front of the slot (never stored)
-  e.fthr = 8u * FLUSH_AT;  // fpos = 0
-  e.err = 0;
-  e.ring = a.tab_bytes + 4u * (wave * ENC_RING * 64 + ring_col(lane));
+  cuwg_enc_init(e, ch.al, a.tab_bytes, wave, lane);
 
-  const uint16_t* sp = syms + s0;
+  const uint16_t* sp = syms + ch.s0;
   // (n <= 2^25 here: the symbol counters are 32-bit, which keeps the tile registers free)
-  const u32 nn = (u32)n;
+  const u32 nn = (u32)ch.n;
   // symbols before the first 64-B aligned tile (the stream is 2-B aligned)
   u32 head = ((64 - ((u32)(uintptr_t)sp & 63)) & 63) >> 1;
   if (head > nn) head = nn;
@@ -158,11 +120,7 @@ __global__ __launch_bounds__(1024) void k_encode_wide(
   }
   // body, part 1: the tiles every live lane of the wave has, with every lane active; dead lanes
   // run along on a dummy tile and a slot with no writable bytes
-  u32 tm = live ? ntile : ~0u;
-#pragma unroll
-  for (int o = 32; o; o >>= 1) tm = min(tm, (u32)__shfl_xor((int)tm, o));
-  if (tm == ~0u) tm = 0;  // no live lane in this wave
-  const u32 tmin = __builtin_amdgcn_readfirstlane(tm);  // wave-uniform (scalar) trip count
+  const u32 tmin = cuwg_tmin(live, ntile);
   const uint8_t* tp = live ? reinterpret_cast<const uint8_t*>(sp + head)
                            : reinterpret_cast<const uint8_t*>(g_wsink);
   // 32-symbol tiles, 4 x 16 B per lane, the next tile in flight while the current one is coded
@@ -209,29 +167,10 @@ __global__ __launch_bounds__(1024) void k_encode_wide(
     if ((j & 7) == 7) enc_flush(e, lane, wring, wout, wrank);
   }
 
-  // Encoder::finish (encoder.rs:40-46): 8 x left_shift
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    enc_emit_byte(e, (u32)(e.low >> 56));
-    e.low <<= 8;
-  }
-  const u32 len = (e.B >> 3) - al;
-  u32 wend = enc_wpos(e);
-  if (e.B & 31) {  // the last, incomplete dword
-    ring_put(e.ring, (e.B >> 5) & (ENC_RING - 1), (u32)(e.acc << (32 - (e.B & 31))));
-    wend += 4;
-  }
-  // final rounds: the last (partial) units, clipped to the stream end
-  const u32 end = al + len;
-  if (end < s_out[tid].hi_ok) s_out[tid].hi_ok = end;
-  while (__any((int)(enc_fpos(e) < wend)))
-    enc_round(e, enc_fpos(e) < wend, lane, wring, wout, wrank);
-  if (live) {
-    e.err = (e.err >> 24) ? wide_first_error(a.row, m.n, sp, n) : 0u;
-    if (!e.err && (u64)len > cap) e.err = RC_F_CAPACITY;
-    out_len[k] = too_long ? 0u : len;
-    flags[k] = too_long ? RC_F_TOO_LONG : e.err;
-  }
+  const u32 len = cuwg_enc_finish(e, &l.out[tid], ch.al, lane, wring, wout, wrank);
+  if (live)
+    cuwg_enc_report(ch, k, len, (e.err >> 24) ? wide_first_error(a.row, m.n, sp, ch.n) : 0u,
+                    out_len, flags);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -255,44 +194,13 @@ struct WideDec : Dec<DEC_LD, 0> {
 typedef Dec<DEC_LD, 0> WideDec;
 #endif
 
-// (cum, c) of symbol s from the cum-only row at LDS byte address rowa: c = cum[s + 1] - cum[s]
-// (the row holds cum[0 .. n], cum[n] the total), one ds_read2_b32
-static __device__ __forceinline__ uint2 wide_row_entry(u32 rowa, u32 s) {
-  const l_u32* rp = (const l_u32*)(uintptr_t)(rowa + (s << 2));
-  const u32 c0 = rp[0], c1 = rp[1];
-  return make_uint2(c0, c1 - c0);
-}
-
-// dec_fix (rc_decode.inc) over the wide cum-only row: the exact index s = #{ j in [1, n-1] :
-// r * cum[j] <= x } (FreqTable::find_index), walked from the candidate.  A copy, not a second
-// form of dec_fix or set_dec_fix (which mask the symbol to 8 bits): changing those changes the
-// generated code of the existing kernels.
-static __device__ __forceinline__ void wide_dec_fix(u32& s, uint2& t, u64& A, u64& B, u64 x,
-                                                    u64 r, u32 rowa, u32 n) {
-  if (A > x) {
-    do {  // (ends at s = 0 at the latest: cum[0] = 0)
-      --s;
-      t = wide_row_entry(rowa, s);
-      A = r * (u64)t.x;
-    } while (A > x);
-    B = r * (u64)t.y;
-  } else {
-    while (s + 1 < n && x - A >= B) {
-      ++s;
-      t = wide_row_entry(rowa, s);
-      A = r * (u64)t.x;
-      B = r * (u64)t.y;
-    }
-  }
-}
-
 // Decoder::decode(&table) with FreqTable::find_index: the hint q from the carried scale G, q's
 // bucket (the buckets are at LDS address 0), which names the symbols [s_lo, s_hi] that find_index
 // returns for the bucket's frequencies, a binary search for the last symbol of that range whose
 // cum is <= q (strides from a.top_stride down, the count that settles the table's widest bucket,
 // so the loop is wave-uniform and scalar; a settled lane probes on without moving), the
 // candidate's (cum, c), the exact u64 verification r cum <= x < r (cum + c), and the exact walk
-// (wide_dec_fix) when a lane's candidate fails it.  Every probe stays inside [s_lo, s_hi],
+// (cuwg_dec_fix) when a lane's candidate fails it.  Every probe stays inside [s_lo, s_hi],
 // whatever the hint.
 template <int DIV>
 static __device__ __forceinline__ u32 wide_dec_sym(WideDec& d, const WideArgs& a, u32 rowa) {
@@ -317,7 +225,7 @@ static __device__ __forceinline__ u32 wide_dec_sym(WideDec& d, const WideArgs& a
     const u32 cm = *(const l_u32*)(uintptr_t)(rowa + (cand << 2));
     s = mselc(smask(q - cm), s, cand);  // (sign set: cum[cand] > q; both are below 2^23)
   }
-  uint2 t = wide_row_entry(rowa, s);
+  uint2 t = cuwg_cum_entry(rowa, s);
   float tc = m.ftotal * __builtin_amdgcn_rcpf(cvt_f32(t.y));  // (hint only)
   u64 B = mul_rv<1>(r, t.y);
   u64 A = mul_rv<1>(r, t.x);
@@ -330,7 +238,7 @@ static __device__ __forceinline__ u32 wide_dec_sym(WideDec& d, const WideArgs& a
     d.st_fix += 1;
 #endif
     if (dx >= B) {
-      wide_dec_fix(s, t, A, B, d.x(), r, rowa, m.n);
+      cuwg_dec_fix<false>(s, t, A, B, d.x(), r, rowa, m.n);
       tc = m.ftotal * __builtin_amdgcn_rcpf(cvt_f32(t.y));
       // the search only lands on symbols with c > 0, so c == 0 can only come from the walk:
       // corrupt input (the reference loops forever); an over-read, if any, came first
@@ -478,20 +386,16 @@ __global__ __launch_bounds__(1024) void k_decode_wide(
     op[i] = (uint16_t)wide_dec_sym<DIV>(d, a, rowa);
     dec_check4<1>(d);
   }
-  // shift_left_buffer panics once more bytes are needed than the stream holds (decoder.rs:33)
-  if (!d.err && d.bpos > d.limb) d.err = RC_F_TRUNCATED;
 #ifdef RC_WIDE_STATS
   atomicAdd(&g_wide_stats[0], (unsigned long long)d.st_steps);
   atomicAdd(&g_wide_stats[1], (unsigned long long)d.st_fix);
 #endif
-  flags[k] = d.err;
+  flags[k] = cuwg_dec_flag(d);
 }
 
 // ------------------------------------------------------------------------------------------
 // Host: the plan and the launchers
 // ------------------------------------------------------------------------------------------
-static u32 wide_bitlen(u32 v) { return v ? 32u - (u32)__builtin_clz(v) : 0u; }
-
 void rc_wide_plan(u32 n, u32 total, WidePlan* p) {
   memset(p, 0, sizeof *p);
   if (n < 1 || n > RC_MAX_WIDE_SYMBOLS || total < 256 || total > 65536) return;
@@ -516,33 +420,7 @@ void rc_wide_plan(u32 n, u32 total, WidePlan* p) {
   // by 2^12 (the single-table decoders' finest) and by the total.  The first of 1,024, 768 and
   // 512 lanes that leaves the cap's buckets room (1,024 at every accepted n: 16 KiB + 16 KiB +
   // 72 KiB at most), else the one that leaves the most.
-  const u32 bl = wide_bitlen(total - 1);
-  const u32 cap = bl < 12u ? bl : 12u;
-  auto bits_at = [&](u32 lanes) -> int {
-    const u32 fixed = (n + 1) * 4u + lanes * SET_DEC_LANE_BYTES;
-    int b = -1;
-    for (u32 t = 0; t <= cap; ++t)
-      if (fixed + (4u << t) <= SET_LDS_BYTES) b = (int)t;
-    return b;
-  };
-  u32 best_lanes = 0;
-  int best = -1;
-  for (u32 lanes = 1024; lanes >= 512; lanes -= 256) {
-    const int b = bits_at(lanes);
-    if (b >= (int)cap) {
-      best_lanes = lanes;
-      best = b;
-      break;
-    }
-    if (b > best) {
-      best_lanes = lanes;
-      best = b;
-    }
-  }
-  p->dec_lanes = best_lanes;
-  p->dec_bits = (u32)best;
-  p->dec_shift = bl > p->dec_bits ? bl - p->dec_bits : 0u;
-  p->dec_lds = (n + 1) * 4u + (4u << p->dec_bits) + best_lanes * SET_DEC_LANE_BYTES;
+  cuwg_dec_plan(p, total, (n + 1) * 4u, 1u, 12u);
 }
 
 hipError_t rc_wide_encode_launch(hipStream_t stream, const RcKnobs& k, const WideArgs& a_in,
@@ -551,25 +429,13 @@ hipError_t rc_wide_encode_launch(hipStream_t stream, const RcKnobs& k, const Wid
                                  const u64* out_off, u64* out_len, u32* flags) {
   WideArgs a = a_in;
   a.tab_bytes = p.enc_tab;
-  hipError_t lds_err = hipSuccess;
-  const u32 lanes = set_launch_lanes(p.enc_lanes, n_chunks);
-  const u32 lds = p.enc_tab + lanes * SET_ENC_LANE_BYTES;
-  const dim3 grid((n_chunks + lanes - 1) / lanes), block(lanes);
   auto go = [&](auto kern) {
-    if ((lds_err = set_allow_lds(reinterpret_cast<const void*>(kern))) != hipSuccess) return;
-    rc_prio_policy(a.m, kPrioEncoder, grid.x,
-                   rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)lanes, lds), k);
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a, syms, sym_off, n_chunks, out, out_off,
-                       out_len, flags);
+    return cuwg_launch(kern, stream, k, a, a.m, kPrioEncoder, p.enc_lanes, SET_ENC_LANE_BYTES,
+                       p.enc_lds, n_chunks, syms, sym_off, n_chunks, out, out_off, out_len, flags);
   };
-  if (div == DIV_POW2) {
-    if (p.enc_layout == 0) go(k_encode_wide<DIV_POW2, 0>);
-    else go(k_encode_wide<DIV_POW2, 1>);
-  } else {
-    if (p.enc_layout == 0) go(k_encode_wide<DIV_MAGIC, 0>);
-    else go(k_encode_wide<DIV_MAGIC, 1>);
-  }
-  return lds_err != hipSuccess ? lds_err : hipGetLastError();
+  if (div == DIV_POW2)
+    return p.enc_layout == 0 ? go(k_encode_wide<DIV_POW2, 0>) : go(k_encode_wide<DIV_POW2, 1>);
+  return p.enc_layout == 0 ? go(k_encode_wide<DIV_MAGIC, 0>) : go(k_encode_wide<DIV_MAGIC, 1>);
 }
 
 hipError_t rc_wide_decode_launch(hipStream_t stream, const RcKnobs& k, const WideArgs& a_in,
@@ -577,18 +443,10 @@ hipError_t rc_wide_decode_launch(hipStream_t stream, const RcKnobs& k, const Wid
                                  const u64* code_off, const u64* code_len, uint16_t* syms_out,
                                  const u64* sym_off, u32 n_chunks, u32* flags) {
   WideArgs a = a_in;
-  hipError_t lds_err = hipSuccess;
-  const u32 lanes = set_launch_lanes(p.dec_lanes, n_chunks);
-  const u32 lds = p.dec_lds - (p.dec_lanes - lanes) * SET_DEC_LANE_BYTES;
-  const dim3 grid((n_chunks + lanes - 1) / lanes), block(lanes);
   auto go = [&](auto kern) {
-    if ((lds_err = set_allow_lds(reinterpret_cast<const void*>(kern))) != hipSuccess) return;
-    rc_prio_policy(a.m, kPrioDecoder512, grid.x,
-                   rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)lanes, lds), k);
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a, code, code_off, code_len, syms_out,
-                       sym_off, n_chunks, flags);
+    return cuwg_launch(kern, stream, k, a, a.m, kPrioDecoder512, p.dec_lanes, SET_DEC_LANE_BYTES,
+                       p.dec_lds, n_chunks, code, code_off, code_len, syms_out, sym_off, n_chunks,
+                       flags);
   };
-  if (div == DIV_POW2) go(k_decode_wide<DIV_POW2>);
-  else go(k_decode_wide<DIV_MAGIC>);
-  return lds_err != hipSuccess ? lds_err : hipGetLastError();
+  return div == DIV_POW2 ? go(k_decode_wide<DIV_POW2>) : go(k_decode_wide<DIV_MAGIC>);
 }
