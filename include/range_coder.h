@@ -82,6 +82,10 @@ typedef struct rc_ctx rc_ctx;     /* one device + one stream; use one per host t
  *   RC_PRIO=off             wave priorities off (every launch oldest-first)
  *   RC_DEC_PAIR=512|1024    decode 2^15 < total <= 2^16 static models with the pair-bucket
  *                           decoder in workgroups of that size (measurements; slower)
+ *   RC_DEC_PAIR=6           decode every 2048 < total <= 2^16 static model through the direct
+ *                           q-to-symbol table (1,024-lane workgroups) at every launch size
+ *   RC_DEC_PAIR=4           decode them through the bucket table at every launch size (unset:
+ *                           chosen per launch from its chunk count and the device's CU count)
  *   RC_STREAM_SERVICE=0     per-call stream entry points launch a kernel per call instead of
  *                           using the stream-service wave
  *   RC_STREAM_DMA=1         host pipeline (rc_*_host): every transfer by DMA engine copies

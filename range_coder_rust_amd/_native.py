@@ -138,6 +138,11 @@ def load():
     L.rc_model_set_check_.restype = _I
     L.rc_model_set_plan_.argtypes = [_U32, _U32, _P]
     L.rc_model_set_plan_.restype = _I
+    # host-only hook: the direct-table decoder's q-to-symbol table (tests/test_direct_table.py;
+    # a library of an earlier revision, tools/build_rev.sh, has none)
+    if hasattr(L, "rc_symof_table_"):
+        L.rc_symof_table_.argtypes = [_U32, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U32)]
+        L.rc_symof_table_.restype = _I
     L.rc_model_create_static_wide.argtypes = [_P, _U32, _P, _P, _U32, ctypes.POINTER(_P)]
     L.rc_encode_batch_wide.argtypes = [_P, _P, _P, _P, _U32, _P, _P, _P, _P]
     L.rc_decode_batch_wide.argtypes = [_P, _P, _P, _P, _P, _P, _P, _U32, _P]

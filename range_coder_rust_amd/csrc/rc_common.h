@@ -266,7 +266,9 @@ hipError_t rc_adaptive_decode_launch(hipStream_t stream, const AdaptParams& p,
 struct RcKnobs {
   bool prio;               // RC_PRIO=off: every wave at priority 0 (oldest-first issue)
   u32 dec_pair;            // RC_DEC_PAIR=512 | 1024: the pair-bucket decoder (LUT 3) for the
-                           //   models that carry its table (tests and measurements)
+                           //   models that carry its table (tests and measurements);
+                           //   6 | 4: small bucket models always through the direct
+                           //   q-to-symbol table (LUT 6) | always through the buckets (LUT 4)
   bool stream_service;     // RC_STREAM_SERVICE=0: the per-call stream API always launches
   bool stream_dma;         // RC_STREAM_DMA=1: the host pipeline moves everything by DMA
   bool stream_direct;      // RC_STREAM_DIRECT=0: the host pipeline stages outputs in HBM

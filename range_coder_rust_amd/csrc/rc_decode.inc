@@ -287,9 +287,10 @@ static __device__ __forceinline__ u32 put_byte(u32 w, u32 v, int j) {
 // (cum, c) table entry)
 template <int SM, int LUT>
 struct GCarry {
-  static constexpr bool on = LUT == 2 || LUT == 5 || ((LUT == 0 || LUT == 3 || LUT == 4) && SM);
+  static constexpr bool on =
+      LUT == 2 || LUT == 5 || ((LUT == 0 || LUT == 3 || LUT == 4 || LUT == 6) && SM);
   static constexpr float scale = LUT == 2 ? 16.0f : 1.0f;
-  static constexpr u32 tab_stride = ((LUT == 0 || LUT == 4) && SM) ? 4u : 2u;  // u32 per entry
+  static constexpr u32 tab_stride = ((LUT == 0 || LUT == 4 || LUT == 6) && SM) ? 4u : 2u;  // u32 per entry
 };
 
 // the carried hint scale, exactly (from the top 32 bits of range)
@@ -491,6 +492,21 @@ static __device__ __forceinline__ u32 dec_sym(D& d, const ModelArgs& m, const u3
     t = make_uint2(te.x, te.y);
     tc = __uint_as_float(te.z);
     s = te.w;
+  } else if (LUT == 6) {
+    // small bucket models, one byte per q: the symbol at the masked hint (the table is the
+    // kernel's first LDS object, so q is its byte address), then the symbol's 16-B entry
+    // {cum, c, total/c, 0} right after the table, at byte symof_mask + 1 + 16 s (one
+    // v_lshl_add_u32: the base is wave-uniform).  No entry of this table straddles a symbol
+    // boundary, so there is no candidate to choose: no compare, no select, no VCC.
+    const u32 q = hint_floor(X, d.G) & m.symof_mask;
+    s = *(const __attribute__((address_space(3))) uint8_t*)(uintptr_t)q;
+    // (written out: from C the compiler splits it into a shift and an add of the mask, with
+    // the + 1 as the read's offset)
+    u32 ta;
+    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(ta) : "v"(s), "s"(m.symof_mask + 1u));
+    const u32x4 te = *(const __attribute__((address_space(3))) u32x4*)(uintptr_t)ta;
+    t = make_uint2(te.x, te.y);
+    tc = __uint_as_float(te.z);
   } else if (LUT) {  // direct table: candidate symbol and its (cum, c) in one LDS read at byte 4q
     // the LUT is the kernel's first LDS object (address 0): q4 is its LDS byte address
     const u32 q4 = hint_floor(X, (4.0f * m.ftotal) * rR) & (m.lut_max << 2);
@@ -652,15 +668,17 @@ __global__ __launch_bounds__(WGS) RC_DEC_ATTR void k_decode_static(
   extern __shared__ u32 s_dyn[];
   u32* s_lut = LUT == 4 ? s_dyn + SMB_TAB_WORDS : s_dyn;
   // LUT words (pair buckets: the symbol pairs, then the 16-B entries; LUT 4: 8-B buckets)
+  // (LUT 6: the q-to-symbol bytes, a power of two >= 4096 of them)
   const u32 lut_n = LUT == 5 ? 0u
+                    : LUT == 6 ? (m.symof_mask + 1) / 4u
                     : LUT == 3 ? PAIR_WORDS : (m.lut_max + 1) * (LUT == 2 ? 4u : LUT == 4 ? 2u : 1u);
   const u32 lut_words = (lut_n + 3) & ~3u;                    // 16-B aligned s_tab
   // (direct tables hold (cum, c) themselves, and pair buckets both candidates: then only the
   // rare exact fix-up reads the table, from global memory)
-  constexpr bool tab_lds = !LUT || LUT == 4 || (DEC_TAB_LDS && LUT != 3);
+  constexpr bool tab_lds = !LUT || LUT == 4 || LUT == 6 || (DEC_TAB_LDS && LUT != 3);
   typedef GCarry<SM, LUT> GC;
   const u32* s_tab = LUT == 4 ? s_dyn : tab_lds ? s_dyn + lut_words : (const u32*)m.tab;
-  const u32* lut_src = LUT == 3 ? m.pair : m.lut;
+  const u32* lut_src = LUT == 3 ? m.pair : LUT == 6 ? (const u32*)m.symof : m.lut;
   const u32 tid = threadIdx.x;
   if (tab_lds && tid < 256) {
     const uint2 e = m.tab[tid];
@@ -819,9 +837,33 @@ namespace {
 // created with RC_DEC_PAIR set (tests and measurements).
 u32 pair_wgs(const RcKnobs& k, const ModelArgs& a, int sm) {
   if (!a.pair || !sm || a.direct) return 0;
-  return k.dec_pair;
+  return k.dec_pair == 512 || k.dec_pair == 1024 ? k.dec_pair : 0;
+}
+
+// Whether a launch of a small bucket model decodes through the direct q-to-symbol table (LUT 6,
+// SYMOF_WG lanes, one workgroup per CU) instead of the buckets (LUT 4).  RC_DEC_PAIR=6 / =4 force
+// one or the other for every model that carries the table (tests and measurements).  Otherwise
+// the models with 2^12 buckets (LUT 4's 512-lane class) take it once the grid gives every
+// workgroup slot of the device SYMOF_MIN_ROUNDS workgroups; `resident` is what the device holds
+// of them at once (its CU count, from the runtime).  A smaller launch, the 2^17-chunk shard
+// among them, would leave CUs idle at 1,024 lanes and keeps LUT 4 (DESIGN.md §5.2).
+#ifndef SYMOF_MIN_ROUNDS
+#define SYMOF_MIN_ROUNDS 1u
+#endif
+bool symof_launch(const RcKnobs& k, const ModelArgs& a, u32 n_chunks, u32 resident) {
+  if (k.dec_pair == 6) return true;
+  if (!resident) return false;
+  return (n_chunks + SYMOF_WG - 1) / SYMOF_WG >= SYMOF_MIN_ROUNDS * resident;
+}
+// (the launches that can take it at all: the model carries the table, and the switch does not
+// force the buckets; unforced, only LUT 4's 512-lane class)
+bool symof_candidate(const RcKnobs& k, const ModelArgs& a, int sm) {
+  if (!a.symof || !sm || a.direct || k.dec_pair == 4) return false;
+  return k.dec_pair == 6 || SMB_WG(a.lut_max + 1) == 512;
 }
 }  // namespace
+
+hipError_t set_allow_lds(const void* kernel);  // rc_indexed.hip: a whole CU's LDS as dynamic LDS
 
 #if RC_DEC_DIV == 0
 hipError_t rc_static_decode_launch_pow2(
@@ -844,9 +886,19 @@ hipError_t rc_static_decode_launch_magic(
   };
   const u32 pw = pair_wgs(k, a, sm);
   if (pw) {
-    const size_t lds = rc_static_decode_lds(a, 1, pw);
+    const size_t lds = rc_static_decode_lds(a, 3, pw);
     if (pw == 1024) return go(k_decode_static<RC_DEC_DIV, 1, 3, 1024>, 1024, lds, kPrioDecoder512);
     return go(k_decode_static<RC_DEC_DIV, 1, 3, 512, DEC_PAIR512_LD>, 512, lds, kPrioDecoder512);
+  }
+  if (symof_candidate(k, a, sm)) {
+    const auto kern = k_decode_static<RC_DEC_DIV, 1, 6, SYMOF_WG>;
+    const size_t lds = rc_static_decode_lds(a, 6, SYMOF_WG);
+    // (more than 64 KiB of dynamic LDS: allowed once per device, before the occupancy query)
+    const hipError_t e = set_allow_lds(reinterpret_cast<const void*>(kern));
+    if (e != hipSuccess) return e;
+    if (symof_launch(k, a, n_chunks,
+                     rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)SYMOF_WG, lds)))
+      return go(kern, SYMOF_WG, lds, kPrioDecoder1024);
   }
 #ifdef RC_SMB_WG  // scratch builds: every small bucket model in workgroups of RC_SMB_WG lanes
   if (sm && !a.direct)
@@ -876,11 +928,13 @@ hipError_t rc_static_decode_launch_magic(
 }
 
 #if RC_DEC_DIV == 0
-size_t rc_static_decode_lds(const ModelArgs& a, int lut3, u32 wgs) {
+size_t rc_static_decode_lds(const ModelArgs& a, int lut, u32 wgs) {
   // LUT (8-B aligned), the (cum, c) table (16-B entries for small bucket models, which carry
   // total / c too; none for pair buckets), the code rings
   const size_t rings = (wgs / 64) * DEC_RING_ALLOC * 64 * sizeof(u32);
-  if (lut3) return PAIR_WORDS * sizeof(u32) + rings;
+  if (lut == 3) return PAIR_WORDS * sizeof(u32) + rings;
+  // the q-to-symbol bytes, the 16-B entries, the rings (at most 143,360 B: rc_static.h)
+  if (lut == 6) return (size_t)a.symof_mask + 1 + 256 * 16 + rings;
   const bool dl = a.direct != 0, dl2 = a.direct == 2;
   const bool sm = a.total >= 256 && a.total <= 65536;
   const bool smb = sm && !dl;  // LUT 4: 8-B buckets and the 16-B symbol table

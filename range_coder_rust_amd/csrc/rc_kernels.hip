@@ -79,7 +79,7 @@ RcKnobs rc_knobs_from_env() {
   k.dec_pair = 0;
   if ((e = str("RC_DEC_PAIR"))) {
     const long x = strtol(e, nullptr, 10);
-    k.dec_pair = x == 512 || x == 1024 ? (u32)x : 0u;
+    k.dec_pair = x == 512 || x == 1024 || x == 4 || x == 6 ? (u32)x : 0u;
   }
   k.stream_service = !((e = str("RC_STREAM_SERVICE")) && e[0] == '0');
   k.stream_dma = (e = str("RC_STREAM_DMA")) && e[0] != '0';
@@ -222,6 +222,19 @@ static std::vector<u32> bucket_table(u32 n_symbols, const u32* c_freq, const u32
   while (lt.size() & (lt.size() - 1)) lt.push_back(lt.back());
   *shift_out = shift;
   return lt;
+}
+
+// The direct-table decoder's q-to-symbol bytes (k_decode_static LUT 6, rc_static.h) of a checked
+// table with 2048 < total <= 2^16: symof[q] = the symbol s with cum[s] <= q < cum[s] + c[s] for
+// every q < total (a symbol with c == 0 owns no entry), padded to a power of two with the last
+// entry (the kernel masks the index, so the padding must name symbols with c > 0 too)
+static std::vector<uint8_t> symof_table(u32 n_symbols, const u32* c_freq, const u32* cum_freq,
+                                        u32 total_freq) {
+  std::vector<uint8_t> t((size_t)1 << bitlen(total_freq - 1));
+  for (u32 s = 0; s < n_symbols; ++s)
+    for (u32 q = cum_freq[s]; q < cum_freq[s] + c_freq[s]; ++q) t[q] = (uint8_t)s;
+  for (size_t q = total_freq; q < t.size(); ++q) t[q] = t[total_freq - 1];
+  return t;
 }
 
 // rc_model_create_static's checks of one row against a given total
@@ -583,6 +596,12 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
     a.lut_max = (u32)lt.size() - 1;
     lut.swap(l8);
   }
+  // the same class through the direct q-to-symbol table (the decoder's LUT 6)
+  std::vector<uint8_t> symof;
+  if (!a.direct && total_freq <= 65536) {
+    symof = symof_table(n_symbols, c_freq, cum_freq, total_freq);
+    a.symof_mask = (u32)symof.size() - 1;
+  }
   const size_t tab_bytes = 256 * sizeof(uint2);
   const size_t lut_bytes = lut.size() * sizeof(u32);
   const size_t pair_bytes = pair.size() * sizeof(u32);
@@ -590,11 +609,15 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
   char* d = nullptr;
   const rc_status up = model_upload(
       ctx, RC_KIND_STATIC, total_freq,
-      {{tab.data(), tab_bytes}, {lut.data(), lut_bytes}, {pair.data(), pair_bytes}}, &mm, &d);
+      {{tab.data(), tab_bytes}, {lut.data(), lut_bytes}, {pair.data(), pair_bytes},
+       {symof.data(), symof.size()}},
+      &mm, &d);
   if (up != RC_OK) return up;
   a.tab = (const uint2*)d;
   a.lut = (const u32*)(d + tab_bytes);
   a.pair = pair_bytes ? (const u32*)(d + tab_bytes + lut_bytes) : nullptr;
+  // (every segment before it is a multiple of 16 B long: the kernel copies the table as words)
+  a.symof = symof.empty() ? nullptr : (const uint8_t*)(d + tab_bytes + lut_bytes + pair_bytes);
   mm->args = a;
   for (u32 i = 0; i < n_symbols; ++i) mm->c_host[i] = c_freq[i];
   mm->complete = n_symbols == 256;
@@ -680,6 +703,22 @@ rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
                                                    code_off, code_len, syms_out, sym_off, n_chunks,
                                                    flags);
       });
+}
+
+// Internal test hook (not in include/range_coder.h; host only, no device needed): the
+// q-to-symbol table rc_model_create_static builds for a model of the direct-table decoder's class
+// (2048 < total <= 2^16), into out[0 .. cap); *size: its length, a power of two >= total.
+rc_status rc_symof_table_(uint32_t n_symbols, const uint32_t* c_freq, const uint32_t* cum_freq,
+                          uint32_t total_freq, uint8_t* out, uint32_t cap, uint32_t* size) {
+  if (!c_freq || !cum_freq || !out || !size) return RC_E_ARG;
+  if (n_symbols < 1 || n_symbols > 256 || total_freq <= 2048 || total_freq > 65536 ||
+      !table_ok(n_symbols, c_freq, cum_freq, total_freq))
+    return RC_E_BAD_MODEL;
+  const std::vector<uint8_t> t = symof_table(n_symbols, c_freq, cum_freq, total_freq);
+  *size = (u32)t.size();
+  if (t.size() > cap) return RC_E_ARG;
+  memcpy(out, t.data(), t.size());
+  return RC_OK;
 }
 
 // ---- static model sets (rc_indexed.h; kernels in rc_indexed.hip) ----

@@ -104,6 +104,10 @@ struct ModelArgs {
                      // 100 MHz clock (rc_prio_rotate)
   u32 flat;          // 1: the flat model (256 symbols, every c = 1, total 256): cum[s] = s, so
                      // the coders need no table (k_decode_static LUT 5, k_encode_static FLAT)
+  const uint8_t* symof;  // small bucket models (k_decode_static LUT 6; null for every other
+                         // class): symof[q] = the symbol s with cum[s] <= q < cum[s] + c[s], for
+                         // q <= symof_mask (padded past total - 1 with the last such symbol)
+  u32 symof_mask;    // 2^bitlen(total - 1) - 1: the table's size less one (at most 2^16 - 1)
 };
 
 // Wave priority ("the end of a launch").  Every chunk is one lane's serial stream
@@ -142,6 +146,10 @@ static constexpr u32 kRotAuto = 0xFFu;
 static constexpr PrioPolicy kPrioEncoder{0.0f, false, 12u};
 static constexpr PrioPolicy kPrioDecoder{1.0f, false, 0u};
 static constexpr PrioPolicy kPrioDecoder512{0.0f, false, kRotAuto};
+//  * 1,024-lane direct-table decoder (LUT 6: one workgroup per CU, its four waves per SIMD start
+//    and end together): the 512-lane decoder's rotation (Zipf decode at 2^20 chunks 63.0 ms,
+//    72.8 ms with RC_PRIO=off; profiles/direct_table/ab_variants_sweep.json).
+static constexpr PrioPolicy kPrioDecoder1024 = kPrioDecoder512;
 static inline void rc_prio_policy(ModelArgs& a, PrioPolicy dflt, u32 grid, u32 resident,
                                   const RcKnobs& k) {
   a.prio_base = ~0u;
@@ -205,6 +213,17 @@ u32 rc_resident_wgs(const void* kernel, int block, size_t lds);
 #define SMB_WG(lut_entries) ((lut_entries) > 2048u ? 512u : (u32)WG)
 #define SMB_TAB_WORDS 1024u                      // the symbol table
 #define SMB_LUT_OFF (SMB_TAB_WORDS * 4)          // bytes
+
+// The same models through a direct q-to-symbol table (k_decode_static LUT 6): LDS holds
+// ModelArgs::symof, one byte per q, at address 0 (at most 64 KiB), then the 16-B entries
+// {cum, c, total/c, 0} and the rings.  An entry of the table has no symbol boundary inside it, so
+// the step needs no bucket, compare or select: ds_read_u8 at the masked hint, then the
+// candidate's entry.  One 1,024-lane workgroup per CU (4 waves per SIMD, as LUT 4 in 512 lanes).
+#define SYMOF_WG 1024u
+#define SYMOF_MAX_BYTES 65536u
+static_assert(SYMOF_MAX_BYTES + 256u * 16u + (SYMOF_WG / 64u) * DEC_RING_ALLOC * 64u * 4u <=
+                  160u * 1024u,
+              "the direct-table decoder's workgroup must fit one CU's LDS at total 2^16");
 
 // Pair-bucket decoding (LUT 3): models with 2^15 < total <= 2^16 (buckets of 16 frequencies) and
 // every c < 2^16.  A bucket's entry holds both candidates of its bucket table entry, so the
@@ -291,9 +310,9 @@ hipError_t rc_static_encode_launch(hipStream_t stream, const RcKnobs& k, const M
                                    int div, int smv, const uint8_t* syms, const u64* sym_off,
                                    u32 n_chunks, uint8_t* out, const u64* out_off, u64* out_len,
                                    u32* flags);
-// dynamic LDS bytes of k_decode_static for a model (lut3: the pair-bucket variant, wgs lanes
-// per workgroup)
-size_t rc_static_decode_lds(const ModelArgs& a, int lut3, u32 wgs);
+// dynamic LDS bytes of k_decode_static for a model in workgroups of wgs lanes (lut 3: the
+// pair-bucket variant, 6: the direct q-to-symbol table, 0: the model's own)
+size_t rc_static_decode_lds(const ModelArgs& a, int lut, u32 wgs);
 hipError_t rc_static_decode_launch_pow2(hipStream_t stream, const RcKnobs& k, const ModelArgs& a,
                                         int sm,
                                         const uint8_t* code, const u64* code_off,
