@@ -40,6 +40,7 @@ typedef int rc_status;
 #define RC_E_CHUNK (-5)     /* synchronous helpers only: at least one chunk has a flag set */
 #define RC_E_BAD_CONTAINER (-6) /* container header / index malformed or inconsistent */
 #define RC_E_CAPACITY (-7)  /* destination buffer too small (the needed size is reported) */
+#define RC_E_BAD_SYMBOL (-8) /* counts name a symbol outside the alphabet (rc_cluster_contexts) */
 
 /* ---- per-chunk flags (bitwise; the first error of a chunk wins) ----
  * Where the reference panics or never terminates, the kernels flag the chunk instead.      */
@@ -468,6 +469,55 @@ rc_status rc_histogram_wide(rc_ctx* ctx, const void* syms16_dev, const uint64_t*
 rc_status rc_histogram_order1(rc_ctx* ctx, uint32_t n_models, const uint8_t* ctx_map_host,
                               uint32_t first_row, const uint8_t* syms_dev,
                               const uint64_t* sym_off_dev, uint32_t n_chunks, uint64_t* hist_dev);
+
+/* The full pair histogram of a batch: what a context map is fitted from (rc_cluster_contexts).
+ * pair_hist_dev   NULL or 256 x 256 uint64: [p][s] is increased by the number of positions
+ *                 i >= 1 of a chunk with sym[i-1] = p and sym[i] = s
+ * first_hist_dev  NULL or 256 uint64: [s] is increased by the number of non-empty chunks whose
+ *                 symbol 0 is s
+ * Chunk boundaries reset the context: the last symbol of a chunk never pairs with the first of
+ * the next.  Counts are ADDED into the arrays (zero them first) and are exact for any data.
+ * With both results NULL the call does nothing (RC_OK).  Device pointers; stream-ordered.   */
+rc_status rc_histogram_pairs(rc_ctx* ctx, const uint8_t* syms_dev, const uint64_t* sym_off_dev,
+                             uint32_t n_chunks, uint64_t* pair_hist_dev,
+                             uint64_t* first_hist_dev);
+
+/* Pair counts -> a context map of at most max_models classes and a first_row (host only, no
+ * device needed; deterministic): greedy agglomerative clustering under the empirical-entropy
+ * cost(v) = sum over v_s > 0 of v_s * log2(sum(v) / v_s), in f64.
+ * The items are the 256 contexts (row p of pair_hist_host) and a pseudo-context 256, "start of
+ * chunk", whose counts are first_hist_host; an item without samples is not clustered.  One
+ * cluster per item with samples; while more than max_models remain, the pair (a, b) with the
+ * smallest cost(a + b) - cost(a) - cost(b) is merged, ties going to the pair whose (smallest
+ * member of a, smallest member of b) is lexicographically smallest.  Rows are numbered by
+ * ascending smallest member.
+ * ctx_map_out     256 entries: the row of context p; a context without samples gets the row with
+ *                 the largest total count (the lowest such row); entries from n_symbols on are 0
+ * first_row_out   the row of pseudo-context 256 (without samples: as a context without samples)
+ * n_models_out    the number of rows, <= max_models (fewer when fewer items have samples)
+ * cost_bits_out   NULL or the sum of the rows' costs: the ideal bits of the counted symbols
+ *                 under the exact, unquantised rows
+ * RC_E_ARG: a null pointer, max_models outside 1..RC_MAX_SET_MODELS, n_symbols outside 1..256
+ * (or counts that sum past 2^63); RC_E_BAD_SYMBOL: a non-zero count in a row or column >=
+ * n_symbols; RC_E_BAD_MODEL: every count is zero.                                           */
+rc_status rc_cluster_contexts(const uint64_t* pair_hist_host, const uint64_t* first_hist_host,
+                              uint32_t n_symbols, uint32_t max_models, uint8_t* ctx_map_out,
+                              uint32_t* first_row_out, uint32_t* n_models_out,
+                              double* cost_bits_out);
+
+/* Batched ideal code length under an order-1 set, straight from the symbols:
+ * bits_dev[k] = sum over the symbols i of chunk k of log2(total / c[row_i][sym_i]), f64, with
+ * row_0 = first_row and row_i = ctx_map[sym[i-1]] as the order-1 coders pick them (after a
+ * symbol >= n_symbols the next row is row 0, as they stage the map).  A term with c == 0 or a
+ * symbol >= n_symbols makes its chunk +inf; an empty chunk is 0.0; nothing is NaN.
+ * `o1` must be an order-1 set of this context's device (RC_E_ARG for any other kind of model).
+ * Stream-ordered; the call waits for the stream (it reads the set's rows back to price them on
+ * the host, as rc_ideal_bits_wide does).
+ * Accuracy: each chunk is summed as 64 partial sums, each in runs of 16 consecutive symbols,
+ * and a 6-step butterfly, so a finite result is within about (n_k / 64 + 22) * 2^-53 relative
+ * of the exact sum of its n_k terms.                                                        */
+rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms_dev,
+                               const uint64_t* sym_off_dev, uint32_t n_chunks, double* bits_dev);
 
 /* Counts -> (c, cum, total) table (host only, no device needed).
  * target_total == 0: calc_cum's exact table, c = counts (total must stay < 2^32; with

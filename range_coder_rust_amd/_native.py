@@ -42,11 +42,13 @@ EXPORTS = (
     "rc_model_create_order1_set", "rc_encode_batch_order1", "rc_decode_batch_order1",
     "rc_histogram_order1",
     "rc_histogram_wide", "rc_ideal_bits_wide",
+    "rc_histogram_pairs", "rc_cluster_contexts", "rc_ideal_bits_order1",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
 RC_E_BAD_CONTAINER = -6
 RC_E_CAPACITY = -7
+RC_E_BAD_SYMBOL = -8
 CONTAINER_HEADER_BYTES = 64
 
 
@@ -164,11 +166,20 @@ def load():
     L.rc_model_order1_plan_.restype = _I
     L.rc_histogram_wide.argtypes = [_P, _P, _P, _U32, _U32, _P, _P, _P]
     L.rc_ideal_bits_wide.argtypes = [_P, _P, _P, _P, _U32, _P]
+    # fitting an order-1 set (a library of an earlier revision, tools/build_rev.sh, has none of
+    # the three; using one of them with such a library raises AttributeError)
+    fit = ("rc_histogram_pairs", "rc_cluster_contexts", "rc_ideal_bits_order1")
+    old = not hasattr(L, fit[0])
+    if not old:
+        L.rc_histogram_pairs.argtypes = [_P, _P, _P, _U32, _P, _P]
+        L.rc_cluster_contexts.argtypes = [_P, _P, _U32, _U32, _P, ctypes.POINTER(_U32),
+                                          ctypes.POINTER(_U32), ctypes.POINTER(ctypes.c_double)]
+        L.rc_ideal_bits_order1.argtypes = [_P, _P, _P, _P, _U32, _P]
     # host-only hook of the wide histogram (not in the header; tests/test_gpu_wide_build.py)
     L.rc_histogram_wide_copies_.argtypes = [_U32]
     L.rc_histogram_wide_copies_.restype = _U32
     for name in EXPORTS:
-        if name not in ("rc_status_string", "rc_last_error"):
+        if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit):
             getattr(L, name).restype = _I
     _lib = L
     return L

@@ -290,3 +290,8 @@ bool rc_model_is_order1_(const rc_model* m);
 // rc_kernels.hip: a wide static model's cum row (device memory: cum[0 .. n], cum[n] = total), its
 // alphabet size and its device; false for any other kind of model (rc_ideal_bits_wide)
 bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int* device);
+// rc_kernels.hip: an order-1 set's cum rows (device memory: [n_models][257], cum[0 .. 256] with
+// the entries from n_symbols on holding the total), its staged 256-entry map (device memory),
+// first_row, sizes and device; false for any other kind of model (rc_ideal_bits_order1)
+bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** map,
+                           u32* first_row, u32* n_models, u32* n_symbols, int* device);

@@ -128,6 +128,17 @@ bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int*
   *device = m->device;
   return true;
 }
+bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** map,
+                           u32* first_row, u32* n_models, u32* n_symbols, int* device) {
+  if (!m || m->kind != RC_KIND_ORDER1) return false;
+  *rows = m->o1.s.rows;
+  *map = m->o1.map;
+  *first_row = m->o1.first_row;
+  *n_models = m->o1.s.k;
+  *n_symbols = m->o1.s.m.n;
+  *device = m->device;
+  return true;
+}
 
 namespace {
 
@@ -370,6 +381,7 @@ const char* rc_status_string(rc_status s) {
     case RC_E_CHUNK: return "at least one chunk flagged";
     case RC_E_BAD_CONTAINER: return "malformed container";
     case RC_E_CAPACITY: return "destination too small";
+    case RC_E_BAD_SYMBOL: return "symbol outside the alphabet";
     default: return "unknown status";
   }
 }

@@ -12,7 +12,10 @@
 //   * k_ideal_bits is the batched PModel::ideal_code_length (pmodel.rs:14-40): per chunk,
 //     sum over its histogram of count * log2(total / c), in f64;
 //   * k_histogram_wide and k_ideal_bits_wide do both for the 16-bit symbols of wide static
-//     models (up to 4096 bins; the ideal bits straight from the symbols, without a histogram).
+//     models (up to 4096 bins; the ideal bits straight from the symbols, without a histogram);
+//   * k_histogram_order1 counts by context class under a given map; k_histogram_pairs counts the
+//     full 256 x 256 pair histogram, rc_cluster_contexts (host) fits a context map to it, and
+//     k_ideal_bits_order1 prices a batch under an order-1 set (rc_order1.h).
 #include "rc_common.h"
 
 #include <math.h>
@@ -227,6 +230,197 @@ __global__ __launch_bounds__(256) void k_histogram_order1(
     }
   }
   flush();
+}
+
+// k_histogram_pairs: the full 256 x 256 pair histogram of a batch (pair[p][s]: positions i >= 1
+// of a chunk with sym[i-1] = p, sym[i] = s) and the histogram of the chunks' first symbols: the
+// counts a context map is fitted from (rc_cluster_contexts).  65,536 u32 counters are 256 KiB,
+// more than a CU's LDS, so the workgroups are split into O1P_SLICES groups by context: workgroup
+// b belongs to group g = b % O1P_SLICES, reads every symbol of its chunks (chunk-stride within
+// the group, so the groups' workgroups that read one chunk run side by side and share it in
+// L2) and counts only the pairs whose previous symbol lies in [g R, (g + 1) R), R = 256 /
+// O1P_SLICES, into R x 256 u32 counters in LDS; group 0 also counts the first symbols, into 256
+// more.  Lane layout as k_histogram_order1: 16 consecutive symbols and the byte before them,
+// O1P_SUB lanes to a chunk, so a workgroup walks O1P_WG / O1P_SUB chunks at a time (with all its
+// lanes on one chunk, three in four idle on 4-KiB chunks).  Measured (profiles/order1_fit/,
+// DESIGN.md §9.10): two slices of 1024-lane workgroups (129 KiB of LDS, one workgroup and 16
+// waves per CU) beat four and eight slices with up to 32 waves per CU, because every slice
+// reads and unpacks every symbol; u64 atomics straight into the result in L2 were 200 times
+// slower.
+// No counter can wrap: every symbol counted adds one to at most one counter of its workgroup,
+// and the counters are flushed into the u64 results before the workgroup has counted 2^32
+// symbols since the last flush, so none exceeds 2^32 - 1 whatever the data.
+#ifndef O1P_SLICES       // (scratch builds: -DO1P_SLICES=n -DO1P_WG=lanes)
+#define O1P_SLICES 2u
+#endif
+#ifndef O1P_WG
+#define O1P_WG 1024u
+#endif
+#ifndef O1P_SUB
+#define O1P_SUB 256u     // lanes that share a chunk
+#endif
+#define O1P_Q (O1P_WG / O1P_SUB)                  // chunks a workgroup walks at a time
+#define O1P_SEG ((1ull << 31) / O1P_Q)            // symbols of a chunk between two looks at the budget
+#define O1P_ROWS (256u / O1P_SLICES)              // contexts per slice
+#define O1P_WORDS (O1P_ROWS * 256u + 256u)        // the slice's counters, then the first symbols'
+#define O1P_LDS (4u * O1P_WORDS)
+
+__global__ __launch_bounds__(O1P_WG) void k_histogram_pairs(
+    const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
+    u64* __restrict__ pair, u64* __restrict__ first) {
+  extern __shared__ u32 s_pp[];
+  const u32 tid = threadIdx.x;
+  const u32 g = blockIdx.x % O1P_SLICES, w = blockIdx.x / O1P_SLICES;
+  const u32 G = gridDim.x / O1P_SLICES;
+  const u32 base = g * O1P_ROWS;  // the slice's first context
+  const bool do_first = first && g == 0;
+  RC_VGPR_FLOOR_48();
+  if (!pair && !do_first) return;  // (workgroup-uniform)
+  u32* const s_first = s_pp + O1P_ROWS * 256u;
+  for (u32 j = tid; j < O1P_WORDS; j += O1P_WG) s_pp[j] = 0;
+  __syncthreads();
+  auto flush = [&]() {
+    __syncthreads();
+    if (pair) {
+      for (u32 j = tid; j < O1P_ROWS * 256u; j += O1P_WG) {
+        const u32 v = s_pp[j];
+        if (v) {
+          atomicAdd(reinterpret_cast<unsigned long long*>(pair + base * 256u + j),
+                    (unsigned long long)v);
+          s_pp[j] = 0;
+        }
+      }
+    }
+    if (do_first && tid < 256) {
+      const u32 v = s_first[tid];
+      if (v) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(first + tid), (unsigned long long)v);
+        s_first[tid] = 0;
+      }
+    }
+    __syncthreads();
+  };
+  u64 pending = 0;  // symbols counted since the last flush (workgroup-uniform)
+  const u32 sub = tid / O1P_SUB, t = tid % O1P_SUB;
+  // a round: O1P_Q consecutive chunks, one per O1P_SUB lanes.  Every thread reads the round's
+  // lengths, so the budget and the flush (which has barriers) stay workgroup-uniform while the
+  // sub-groups walk chunks of different lengths.
+  for (u32 k0 = w * O1P_Q; k0 < n_chunks; k0 += G * O1P_Q) {
+    u64 len[O1P_Q], nmax = 0;
+#pragma unroll
+    for (u32 q = 0; q < O1P_Q; ++q) {
+      len[q] = k0 + q < n_chunks ? sym_off[k0 + q + 1] - sym_off[k0 + q] : 0;
+      nmax = len[q] > nmax ? len[q] : nmax;
+    }
+    const u32 k = k0 + sub;
+    const u64 s0 = k < n_chunks ? sym_off[k] : 0, n = k < n_chunks ? sym_off[k + 1] - s0 : 0;
+    const uint8_t* p = syms + s0;
+    for (u64 b0 = 0; b0 < nmax; b0 += O1P_SEG) {
+      u64 cnt = 0;  // at most O1P_Q * O1P_SEG = 2^31
+#pragma unroll
+      for (u32 q = 0; q < O1P_Q; ++q)
+        cnt += len[q] > b0 ? (len[q] - b0 < O1P_SEG ? len[q] - b0 : O1P_SEG) : 0;
+      if (pending + cnt > 0xFFFFFFFFull) {
+        flush();
+        pending = 0;
+      }
+      pending += cnt;
+      if (b0 >= n) continue;
+      const u64 b1 = n - b0 < O1P_SEG ? n : b0 + O1P_SEG;
+      if (!pair) {  // first symbols only
+        if (b0 == 0 && t == 0) atomicAdd(&s_first[p[0]], 1u);
+        continue;
+      }
+      for (u64 i = b0 + 16ull * t; i < b1; i += 16ull * O1P_SUB) {
+        // the previous symbol relative to the slice; a chunk's first symbol has none (chunk
+        // boundaries reset the context) and is counted in the first-symbol histogram
+        u32 rel = i ? (u32)p[i - 1] - base : 0x80000000u;
+        if (i == 0 && do_first) atomicAdd(&s_first[p[0]], 1u);
+        if (i + 16 <= b1) {
+          const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
+          const u32 ws[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const u32 s = (ws[q] >> (8 * j)) & 255u;
+              if (rel < O1P_ROWS) atomicAdd(&s_pp[rel * 256u + s], 1u);
+              rel = s - base;
+            }
+          }
+        } else {
+          for (u64 j = i; j < b1; ++j) {
+            const u32 s = p[j];
+            if (rel < O1P_ROWS) atomicAdd(&s_pp[rel * 256u + s], 1u);
+            rel = s - base;
+          }
+        }
+      }
+    }
+  }
+  flush();
+}
+
+// k_ideal_bits_order1: per chunk the sum of icl[row_i][sym_i] over its symbols, row_0 =
+// first_row and row_i = map[sym[i-1]], straight from the symbols: no histogram and no atomics.
+// icl: K x 256 ideal code lengths in f64, +inf where c == 0 and from n_symbols on; it is staged
+// in dynamic LDS once per workgroup (2 K KiB, 128 KiB at K = 64) with the 256-B map behind it
+// (entries from n_symbols on are 0, as the coders stage them).  The table bounds the workgroups
+// per CU, one at K = 64, so the host picks the workgroup size from K to keep 16 waves or more
+// on the CU.  One wave per chunk, waves striding over the chunks (one workgroup per chunk was
+// slower at every K, 2.8 times at K = 64 on 4-KiB chunks: DESIGN.md §9.10); a lane takes 16
+// consecutive symbols and the byte before them (as k_histogram_order1) at a stride of 1024
+// symbols, into a private f64 sum, and a butterfly adds the 64 sums.  Every term is >= 0 or +inf (there is no
+// 0 * inf), so a chunk is +inf or finite, never NaN.  Accuracy: a lane adds at most
+// 16 ceil(n_k / 1024) <= n_k / 64 + 16 non-negative terms one by one and the butterfly adds
+// log2 64 = 6 more steps, so the relative error of a finite chunk of n_k symbols is at most
+// about (n_k / 64 + 22) * 2^-53: below 1e-12 up to n_k = 5.7e5.
+__global__ __launch_bounds__(1024) void k_ideal_bits_order1(
+    const double* __restrict__ icl, const uint8_t* __restrict__ map, u32 first_row, u32 K,
+    const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
+    double* __restrict__ bits) {
+  extern __shared__ double s_o1i[];
+  uint8_t* const s_map = reinterpret_cast<uint8_t*>(s_o1i + K * 256u);
+  const u32 lane = threadIdx.x & 63, waves = blockDim.x >> 6;
+  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (u32 j = threadIdx.x; j < K * 256u; j += blockDim.x) s_o1i[j] = icl[j];
+  if (threadIdx.x < 256) s_map[threadIdx.x] = map[threadIdx.x];
+  __syncthreads();
+  const u32 nw = gridDim.x * waves;
+  for (u32 k = blockIdx.x * waves + wave; k < n_chunks; k += nw) {
+    const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
+    const uint8_t* p = syms + s0;
+    double acc = 0.0;
+    for (u64 i = 16ull * lane; i < n; i += 16ull * 64) {
+      u32 row = i ? (u32)s_map[p[i - 1]] : first_row;  // chunk boundaries reset the context
+      if (i + 16 <= n) {
+        const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
+        const u32 ws[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const u32 s = (ws[q] >> (8 * j)) & 255u;
+            acc += s_o1i[row * 256u + s];
+            row = s_map[s];
+          }
+        }
+      } else {
+        for (u64 j = i; j < n; ++j) {
+          const u32 s = p[j];
+          acc += s_o1i[row * 256u + s];
+          row = s_map[s];
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+      const u64 x = (u64)__double_as_longlong(acc);
+      const u64 y = ((u64)(u32)__shfl_xor((int)hi32(x), o) << 32) | (u32)__shfl_xor((int)(u32)x, o);
+      acc += __longlong_as_double((long long)y);
+    }
+    if (lane == 0) bits[k] = acc;
+  }
 }
 
 // per chunk: bits = sum_i hist[i] * icl[i] in f64 (icl[i] = +inf for c_i == 0: the reference's
@@ -532,6 +726,93 @@ rc_status rc_histogram_order1(rc_ctx* ctx, uint32_t n_models, const uint8_t* ctx
   return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
 }
 
+rc_status rc_histogram_pairs(rc_ctx* ctx, const uint8_t* syms, const uint64_t* sym_off,
+                             uint32_t n_chunks, uint64_t* pair_hist, uint64_t* first_hist) {
+  hipStream_t s;
+  int dev;
+  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (n_chunks == 0 || (!pair_hist && !first_hist)) return RC_OK;
+  if (!syms || !sym_off) return RC_E_ARG;
+  DevSet g(dev);
+  rc_svc_yield_all_();
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return RC_E_DEVICE;
+  if (set_allow_lds(reinterpret_cast<const void*>(k_histogram_pairs)) != hipSuccess)
+    return RC_E_DEVICE;
+  // as many workgroups as the CUs hold (their LDS and 32 waves each), in O1P_SLICES groups that
+  // stride over the chunks side by side
+  const u32 per_cu = std::max(1u, std::min(163840u / O1P_LDS, 2048u / O1P_WG));
+  const u32 groups = std::max(
+      1u, std::min<u32>((n_chunks + O1P_Q - 1) / O1P_Q, (u32)cus * per_cu / O1P_SLICES));
+  hipLaunchKernelGGL(k_histogram_pairs, dim3(groups * O1P_SLICES), dim3(O1P_WG), O1P_LDS, s,
+                     syms, sym_off, n_chunks, pair_hist, first_hist);
+  return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+}
+
+rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,
+                               const uint64_t* sym_off, uint32_t n_chunks, double* bits) {
+  hipStream_t s;
+  int dev, mdev;
+  const u32* rows_dev;
+  const uint8_t* map_dev;
+  u32 first_row, K, n;
+  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (!rc_model_order1_rows_(o1, &rows_dev, &map_dev, &first_row, &K, &n, &mdev))
+    return RC_E_ARG;  // kinds do not mix
+  if (mdev != dev) return RC_E_ARG;
+  if (n_chunks == 0) return RC_OK;
+  if (!syms || !sym_off || !bits) return RC_E_ARG;
+  DevSet g(dev);
+  rc_svc_yield_all_();
+  // the set keeps its tables on the device only (K cum rows cum[0 .. 256], the entries from n on
+  // holding the total): read them back, then PModel::ideal_code_length (pmodel.rs:14-40) per row
+  // and symbol exactly as rc_ideal_bits computes it, +inf for c == 0, which covers the symbols
+  // from n on.  Pinned staging: the rows, then the table, 8-B aligned.
+  const size_t rows_words = (size_t)K * 257u;
+  const size_t rows_bytes = (rows_words * sizeof(u32) + 7) & ~(size_t)7;
+  const size_t icl_bytes = (size_t)K * 256u * sizeof(double);
+  char* pin = (char*)rc_pinned_scratch_(rows_bytes + icl_bytes);
+  if (!pin) return RC_E_DEVICE;
+  if (hipMemcpyAsync(pin, rows_dev, rows_words * sizeof(u32), hipMemcpyDeviceToHost, s) !=
+          hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return RC_E_DEVICE;
+  const u32* cum = (const u32*)pin;
+  double* icl = (double*)(pin + rows_bytes);
+  for (u32 j = 0; j < K; ++j) {
+    const u32* r = cum + (size_t)j * 257u;
+    const double lt = log((double)r[256]);
+    for (u32 i = 0; i < 256; ++i) {
+      const u32 c = r[i + 1] - r[i];
+      icl[(size_t)j * 256u + i] = c > 0 ? (lt - log((double)c)) / M_LN2 : INFINITY;
+    }
+  }
+  double* d = nullptr;
+  if (hipMallocAsync((void**)&d, icl_bytes, s) != hipSuccess) return RC_E_DEVICE;
+  if (hipMemcpyAsync(d, icl, icl_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+      set_allow_lds(reinterpret_cast<const void*>(k_ideal_bits_order1)) != hipSuccess) {
+    (void)hipFreeAsync(d, s);
+    return RC_E_DEVICE;
+  }
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 256;
+  // the table's LDS bounds the workgroups per CU (one at K = 64, 8 at most); the workgroup's
+  // size keeps at least 16 waves on the CU: 1024 lanes where one fits, 512 where two or three
+  // do, else 256 (16 to 32 waves)
+  const u32 lds = (u32)icl_bytes + 256u;
+  const u32 per_cu = std::max(1u, std::min(8u, 163840u / lds));
+  const u32 wg = per_cu == 1 ? 1024u : per_cu < 4 ? 512u : 256u;
+  const u32 grid = std::min<u32>((n_chunks + wg / 64 - 1) / (wg / 64), (u32)cus * per_cu);
+  hipLaunchKernelGGL(k_ideal_bits_order1, dim3(grid), dim3(wg), lds, s, d, map_dev, first_row, K,
+                     syms, sym_off, n_chunks, bits);
+  const bool ok = hipGetLastError() == hipSuccess;
+  // the pinned staging is reused by this thread's next call: wait for the copy
+  const bool fr = hipFreeAsync(d, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  return ok && fr ? RC_OK : RC_E_DEVICE;
+}
+
 rc_status rc_histogram_wide(rc_ctx* ctx, const void* syms, const uint64_t* sym_off,
                             uint32_t n_chunks, uint32_t n_bins, uint32_t* chunk_hist,
                             uint64_t* hist, uint64_t* oob) {
@@ -703,6 +984,109 @@ rc_status rc_quantize_counts_wide(const uint64_t* counts, uint32_t n_symbols,
                                   uint32_t* cum_out, uint32_t* total_out) {
   return quantize_counts(counts, n_symbols, RC_MAX_WIDE_SYMBOLS, target_total, qflags, c_out,
                          cum_out, total_out);
+}
+
+// rc_cluster_contexts: greedy agglomerative clustering of the 256 contexts and the start-of-chunk
+// pseudo-context under the empirical-entropy cost (include/range_coder.h).  A cluster lives in
+// the slot of its smallest member, so scanning the slots in ascending order with a strict
+// comparison is the tie-break.  The pairwise deltas are kept in a table and only the merged
+// cluster's row is recomputed per merge: 256 log2 per pair, about 8 M for the start and 65 k per
+// merge.
+#define CC_ITEMS 257u
+
+// cost(a + b); b may be null
+static double cc_cost(const u64* a, const u64* b) {
+  u64 n = 0;
+  for (u32 s = 0; s < 256; ++s) n += a[s] + (b ? b[s] : 0);
+  const double dn = (double)n;
+  double c = 0.0;
+  for (u32 s = 0; s < 256; ++s) {
+    const u64 t = a[s] + (b ? b[s] : 0);
+    if (t) c += (double)t * log2(dn / (double)t);
+  }
+  return c;
+}
+
+rc_status rc_cluster_contexts(const uint64_t* pair_hist, const uint64_t* first_hist,
+                              uint32_t n_symbols, uint32_t max_models, uint8_t* ctx_map_out,
+                              uint32_t* first_row_out, uint32_t* n_models_out,
+                              double* cost_bits_out) {
+  if (!pair_hist || !first_hist || !ctx_map_out || !first_row_out || !n_models_out ||
+      max_models < 1 || max_models > RC_MAX_SET_MODELS || n_symbols < 1 || n_symbols > 256)
+    return RC_E_ARG;
+  auto item = [&](u32 a) { return a < 256 ? pair_hist + (size_t)a * 256 : first_hist; };
+  unsigned __int128 all = 0;
+  std::vector<u64> tot(CC_ITEMS, 0);  // samples per slot
+  for (u32 a = 0; a < CC_ITEMS; ++a) {
+    const u64* v = item(a);
+    unsigned __int128 t = 0;
+    for (u32 s = 0; s < 256; ++s) {
+      if (v[s] && (s >= n_symbols || (a < 256 && a >= n_symbols))) return RC_E_BAD_SYMBOL;
+      t += v[s];
+    }
+    all += t;
+    if (all >> 63) return RC_E_ARG;
+    tot[a] = (u64)t;
+  }
+  if (all == 0) return RC_E_BAD_MODEL;
+  std::vector<u64> vec((size_t)CC_ITEMS * 256);
+  std::vector<double> cost(CC_ITEMS, 0.0), delta((size_t)CC_ITEMS * CC_ITEMS, 0.0);
+  std::vector<u32> slot(CC_ITEMS), live;  // slot: an item's cluster (CC_ITEMS: not clustered)
+  for (u32 a = 0; a < CC_ITEMS; ++a) {
+    memcpy(&vec[(size_t)a * 256], item(a), 256 * sizeof(u64));
+    slot[a] = tot[a] ? a : CC_ITEMS;
+    if (tot[a]) {
+      live.push_back(a);
+      cost[a] = cc_cost(&vec[(size_t)a * 256], nullptr);
+    }
+  }
+  auto refresh = [&](u32 a, u32 b) {  // a < b, both live
+    delta[(size_t)a * CC_ITEMS + b] =
+        cc_cost(&vec[(size_t)a * 256], &vec[(size_t)b * 256]) - cost[a] - cost[b];
+  };
+  if (live.size() > max_models)
+    for (size_t i = 0; i < live.size(); ++i)
+      for (size_t j = i + 1; j < live.size(); ++j) refresh(live[i], live[j]);
+  while (live.size() > max_models) {
+    size_t bi = 0, bj = 1;
+    double best = INFINITY;
+    for (size_t i = 0; i < live.size(); ++i)
+      for (size_t j = i + 1; j < live.size(); ++j) {
+        const double d = delta[(size_t)live[i] * CC_ITEMS + live[j]];
+        if (d < best) {
+          best = d;
+          bi = i;
+          bj = j;
+        }
+      }
+    const u32 a = live[bi], b = live[bj];
+    // the merged cluster's cost, as cc_cost sums it
+    cost[a] = cc_cost(&vec[(size_t)a * 256], &vec[(size_t)b * 256]);
+    for (u32 s = 0; s < 256; ++s) vec[(size_t)a * 256 + s] += vec[(size_t)b * 256 + s];
+    tot[a] += tot[b];
+    for (u32 x = 0; x < CC_ITEMS; ++x)
+      if (slot[x] == b) slot[x] = a;
+    live.erase(live.begin() + (ptrdiff_t)bj);
+    for (u32 x : live) {
+      if (x < a) refresh(x, a);
+      else if (x > a) refresh(a, x);
+    }
+  }
+  // rows by ascending smallest member (live is ascending); the largest row, lowest on ties
+  std::vector<u32> row(CC_ITEMS + 1, 0);
+  u32 big = 0;
+  double bits = 0.0;
+  for (size_t i = 0; i < live.size(); ++i) {
+    row[live[i]] = (u32)i;
+    if (tot[live[i]] > tot[live[big]]) big = (u32)i;
+    bits += cost[live[i]];
+  }
+  row[CC_ITEMS] = big;  // items without samples
+  for (u32 p = 0; p < 256; ++p) ctx_map_out[p] = p < n_symbols ? (uint8_t)row[slot[p]] : 0;
+  *first_row_out = row[slot[256]];
+  *n_models_out = (u32)live.size();
+  if (cost_bits_out) *cost_bits_out = bits;
+  return RC_OK;
 }
 
 rc_status rc_ideal_bits(rc_ctx* ctx, const uint32_t* c_host, uint32_t n_symbols,

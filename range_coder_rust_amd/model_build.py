@@ -12,6 +12,13 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
   histogram_order1(syms, sym_off, ctx_map, first_row)   rc_histogram_order1: symbol counts by
                                   context class, the previous symbol picking the class (HIP)
   build_order1_set(syms, sym_off, ctx_map)   those counts -> Order1ModelSet, in one call
+  histogram_pairs(syms, sym_off)  rc_histogram_pairs: the full 256 x 256 pair histogram and the
+                                  histogram of the chunks' first symbols (HIP)
+  cluster_contexts(pair, first, K)           rc_cluster_contexts: those counts -> a context map
+                                  of at most K classes and a first_row (host)
+  fit_order1_set(syms, sym_off, K)           pairs -> map -> class counts -> Order1ModelSet
+  ideal_bits_order1(model, syms, sym_off)    rc_ideal_bits_order1: per-chunk ideal bits of an
+                                  order-1 set, straight from the symbols (HIP)
   histogram_wide(syms, sym_off, n_bins)      rc_histogram_wide: the counts of 16-bit symbols (HIP)
   build_wide_model(syms, sym_off, n)         those counts -> WideStaticModel, in one call
   ideal_bits_wide(model, syms, sym_off)      rc_ideal_bits_wide: per-chunk ideal bits of a wide
@@ -132,6 +139,90 @@ def build_order1_set(syms, sym_off, ctx_map, first_row=0, target_total=1 << 16, 
         raise ValueError(f"symbols >= {n_symbols} present")
     return Order1ModelSet.from_counts(counts[:, :n_symbols], _ctx_map256(ctx_map)[:n_symbols],
                                       first_row, target_total, ctx=ctx)
+
+
+def histogram_pairs(syms, sym_off, pair_hist=None, first_hist=None, ctx=None):
+    """rc_histogram_pairs on torch tensors (async, torch's current stream).
+
+    Returns (pair_hist, first_hist): int64[256, 256], [p][s] = the positions i >= 1 of a chunk
+    with sym[i-1] = p and sym[i] = s, and int64[256], [s] = the non-empty chunks whose symbol 0
+    is s.  Chunk boundaries reset the context.  Given arrays are added into."""
+    torch = _torch()
+    _check_dev(syms, "syms", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    ctx = ctx or default_context(syms.device.index)
+    n = sym_off.numel() - 1
+    for name, t, shape in (("pair_hist", pair_hist, (256, 256)), ("first_hist", first_hist, (256,))):
+        if t is not None:
+            _check_dev(t, name, (torch.int64, torch.uint64))
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {list(shape)}")
+    if pair_hist is None:
+        pair_hist = torch.zeros((256, 256), dtype=torch.int64, device=syms.device)
+    if first_hist is None:
+        first_hist = torch.zeros(256, dtype=torch.int64, device=syms.device)
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_histogram_pairs(ctx.handle, _ptr(syms), _ptr(sym_off), n,
+                                        _ptr(pair_hist), _ptr(first_hist)), "rc_histogram_pairs")
+    return pair_hist, first_hist
+
+
+def cluster_contexts(pair_hist, first_hist, n_models=64, n_symbols=256):
+    """rc_cluster_contexts (host): pair counts [256, 256] and first-symbol counts [256] -> a
+    context map of at most n_models classes, by greedy agglomerative clustering under the
+    empirical-entropy cost.
+
+    Returns (ctx_map, first_row, n_models, cost_bits): ctx_map uint8[n_symbols], the class of
+    every previous symbol; first_row, the class of a chunk's start; the number of classes found
+    (fewer than asked for when fewer contexts occur); cost_bits, the ideal bits of the counted
+    symbols under the classes' exact rows."""
+    L = N.load()
+    pair = np.ascontiguousarray(pair_hist, dtype=np.uint64)
+    first = np.ascontiguousarray(first_hist, dtype=np.uint64)
+    if pair.shape != (256, 256) or first.shape != (256,):
+        raise ValueError("pair_hist must be [256, 256] and first_hist [256]")
+    cm = np.zeros(256, np.uint8)
+    first_row, k, cost = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_double()
+    rc = L.rc_cluster_contexts(ctypes.c_void_p(pair.ctypes.data),
+                               ctypes.c_void_p(first.ctypes.data), int(n_symbols), int(n_models),
+                               ctypes.c_void_p(cm.ctypes.data), ctypes.byref(first_row),
+                               ctypes.byref(k), ctypes.byref(cost))
+    if rc == N.RC_E_BAD_SYMBOL:
+        raise ValueError(f"symbols >= {int(n_symbols)} present")
+    if rc == N.RC_E_BAD_MODEL:
+        raise ValueError("no context map for empty counts")
+    N.check(rc, "rc_cluster_contexts")
+    return cm[:int(n_symbols)], int(first_row.value), int(k.value), float(cost.value)
+
+
+def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=256, ctx=None):
+    """An Order1ModelSet fitted to the batch: pair counts on the GPU (histogram_pairs), a context
+    map of at most n_models classes from them (cluster_contexts), the classes' counts on the GPU
+    (histogram_order1 with the map found) and their quantised rows.  The set's ctx_map and
+    first_row are the ones found; it has as many rows as classes were found."""
+    ctx = ctx or default_context(syms.device.index)
+    pair, first = histogram_pairs(syms, sym_off, ctx=ctx)
+    cm, first_row, k, _ = cluster_contexts(pair.cpu().numpy(), first.cpu().numpy(), n_models,
+                                           n_symbols)
+    return build_order1_set(syms, sym_off, cm, first_row, target_total, n_symbols, n_models=k,
+                            ctx=ctx)
+
+
+def ideal_bits_order1(model, syms, sym_off):
+    """rc_ideal_bits_order1: float64[n] tensor, per chunk the sum of log2(total / c[row_i][s_i])
+    over its symbols, row_0 = first_row and row_i = ctx_map[s_(i-1)], straight from the symbols
+    (inf if a term has c == 0 or a symbol >= model.n_symbols; 0.0 for an empty chunk).  model:
+    an Order1ModelSet."""
+    torch = _torch()
+    _check_dev(syms, "syms", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    bits = torch.empty(max(n, 1), dtype=torch.float64, device=syms.device)
+    ctx = model.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_ideal_bits_order1(ctx.handle, model.handle, _ptr(syms), _ptr(sym_off), n,
+                                          _ptr(bits)), "rc_ideal_bits_order1")
+    return bits[:n]
 
 
 def histogram_wide(syms, sym_off, n_bins, per_chunk=False, batch=True, ctx=None):
