@@ -41,6 +41,7 @@ typedef int rc_status;
 #define RC_E_BAD_CONTAINER (-6) /* container header / index malformed or inconsistent */
 #define RC_E_CAPACITY (-7)  /* destination buffer too small (the needed size is reported) */
 #define RC_E_BAD_SYMBOL (-8) /* counts name a symbol outside the alphabet (rc_cluster_contexts) */
+#define RC_E_CHECKSUM (-9)  /* decoded symbols miss a chunk's checksum (rc_container2_verify) */
 
 /* ---- per-chunk flags (bitwise; the first error of a chunk wins) ----
  * Where the reference panics or never terminates, the kernels flag the chunk instead.      */
@@ -594,6 +595,91 @@ rc_status rc_container_info_parse(const uint8_t* head_host, uint64_t head_len,
 rc_status rc_container_offsets(rc_ctx* ctx, const uint8_t* container_dev,
                                const rc_container_info* info, uint64_t* code_off_dev,
                                uint64_t* code_len_dev, uint64_t* sym_off_dev);
+
+/* ---- chunked container "RCB2": order-1 sets, wide models, per-chunk checksums ----
+ * RCB1 frames an order-0 static table or the adaptive model and nothing else, and it stores no
+ * check of the decoded data: a damaged payload byte may decode, unflagged, to other symbols.
+ * RCB2 is a second format beside it (RCB1 and its entry points are unchanged, and
+ * rc_container_info_parse keeps rejecting the magic "RCB2"): it also frames an order-1 set or a
+ * wide static model, and it may carry one 32-bit checksum of the decoded symbols per chunk.
+ * All fields little-endian; every section starts 16-B aligned and is zero padded to 16 B:
+ *   offset 0          header, RC_CONTAINER_HEADER_BYTES:
+ *                       0 "RCB2"  4 u32 version 1 | header bytes << 16
+ *                       8 u32 kind: 0 static, 1 adaptive, 2 order-1 set, 3 wide static
+ *                       12 u32 n_symbols (1..256; 1..RC_MAX_WIDE_SYMBOLS for kind 3)
+ *                       16 u32 total_freq (kinds 0, 2, 3)
+ *                       20/24/28 u32 kind 1: increment/limit/period; kind 2: n_models K
+ *                       (1..RC_MAX_SET_MODELS) / first_row (< K) / 0
+ *                       32 u64 n_chunks  40 u64 symbols in all chunks  48 u64 payload bytes
+ *                       56 u32 flags: RC_CONTAINER2_F_CHECKSUMS, every other bit 0   60 u32 0
+ *   table_off = 64    kinds 0 and 3: n_symbols x u32 c_freq; kind 2: K x n_symbols u32 c_freq,
+ *                     row-major, then n_symbols bytes of ctx_map (at most 64 KiB + 256 B);
+ *                     kind 1: empty.  cum is always rebuilt by calc_cum.
+ *   index_off         n_chunks x {u64 symbol count, u64 code length}, as RCB1
+ *   sum_off           n_chunks x u32 checksums; present only with RC_CONTAINER2_F_CHECKSUMS
+ *   payload_off       the streams as in RCB1: each starts 16-B aligned, zero padded to 16 B
+ * A symbol of kind 3 is two bytes (host byte order = little-endian); all counts are in symbols.
+ *
+ * The checksum of a chunk.  Take its symbols as bytes: L = count x symbol size, in chunk order.
+ *   w_i   = the little-endian u32 of bytes 4i .. 4i+3, zero padded past L, for i < ceil(L / 4)
+ *   S     = sum_i fmix32((w_i + (i + 1) * 0x9E3779B1) mod 2^32)  mod 2^32
+ *   sum   = fmix32(S ^ (u32)L)
+ * with fmix32 MurmurHash3's 32-bit finaliser (h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13;
+ * h *= 0xC2B2AE35; h ^= h >> 16).  The sum over positions is order-free, so the result does not
+ * depend on how a launch splits the chunk; the position term catches moved words; fmix32 is a
+ * bijection, so a change confined to one word always changes the result.  It guards against
+ * accidents (a damaged byte, a truncated or misplaced stream), NOT against an adversary: a
+ * forger can solve for a matching sum, and unrelated damage in several words collides with
+ * probability about 2^-32.                                                                  */
+#define RC_CONTAINER2_F_CHECKSUMS 1u
+typedef struct rc_container2_info {
+  uint32_t version, kind, n_symbols, total_freq, increment, limit, period, reserved;
+  uint64_t n_chunks, n_syms, payload_bytes;
+  uint64_t table_off, index_off, payload_off, container_bytes;
+  uint32_t n_models, first_row, flags, sym_bytes;
+  uint64_t sum_off;
+} rc_container2_info;
+/* The rc_container2_* calls below take and fill an rc_container2_info through a void pointer
+ * (info2): parse marks the struct it fills (reserved = the magic as a u32), and the calls that
+ * read one return RC_E_ARG for a struct without the mark, an rc_container_info included.     */
+
+/* Checksums of n_chunks chunks (device pointers; asynchronous and stream-ordered on the
+ * context's stream, like rc_histogram).  off_dev: n_chunks + 1 offsets in symbols; sym_bytes 1 or
+ * 2 (else RC_E_ARG); chunk k is the bytes [off[k] * sym_bytes, off[k+1] * sym_bytes) of data_dev,
+ * which may start at any address.  sums_dev: n_chunks u32.  No byte outside the chunks is read.*/
+rc_status rc_checksum_batch(rc_ctx* ctx, const void* data_dev, const uint64_t* off_dev,
+                            uint32_t n_chunks, uint32_t sym_bytes, uint32_t* sums_dev);
+/* Parse an RCB2 header (head_host: the first >= RC_CONTAINER_HEADER_BYTES bytes) into *info2.
+ * RC_E_BAD_CONTAINER: wrong magic, version or header size, unknown kind, unknown flag bits,
+ * n_symbols, n_models or first_row out of range, n_chunks > RC_MAX_CHUNKS, payload bytes not a
+ * multiple of 16.                                                                           */
+rc_status rc_container2_info_parse(const uint8_t* head_host, uint64_t head_len, void* info2);
+/* rc_container_pack for RCB2: m is a static, adaptive, order-1 or wide model (RC_E_ARG for a
+ * static set, which has no index stream to frame); sums_dev NULL (no checksum section) or
+ * n_chunks u32 from rc_checksum_batch over the symbols.  Same size-query and capacity protocol:
+ * *dst_len_host receives the size; RC_E_CAPACITY (nothing written) when it exceeds dst_cap or
+ * dst_dev is NULL.  Synchronous.                                                            */
+rc_status rc_container2_pack(rc_ctx* ctx, const rc_model* m, const uint8_t* slots_dev,
+                             const uint64_t* slot_off_dev, const uint64_t* code_len_dev,
+                             const uint64_t* sym_off_dev, uint32_t n_chunks,
+                             const uint32_t* sums_dev, uint8_t* dst_dev, uint64_t dst_cap,
+                             uint64_t* dst_len_host);
+/* rc_container_offsets for RCB2: the same contract. */
+rc_status rc_container2_offsets(rc_ctx* ctx, const uint8_t* container_dev, const void* info2,
+                                uint64_t* code_off_dev, uint64_t* code_len_dev,
+                                uint64_t* sym_off_dev);
+/* The container's model, created from its table section by the rc_model_create_* call of its
+ * kind (destroy it with rc_model_destroy).  A table that call rejects (a row that does not sum
+ * to total_freq, a map entry >= n_models, ...) is RC_E_BAD_CONTAINER.  Synchronous.         */
+rc_status rc_container2_model(rc_ctx* ctx, const uint8_t* container_dev, const void* info2,
+                              rc_model** out);
+/* Compare the checksums of decoded symbols (syms_dev: n_syms symbols of the container's symbol
+ * size; sym_off_dev from rc_container2_offsets) with the stored ones.  RC_OK when the container
+ * has no checksum section or every chunk matches; else RC_E_CHECKSUM with the lowest
+ * mismatching chunk in *first_bad_host.  Synchronous.                                       */
+rc_status rc_container2_verify(rc_ctx* ctx, const uint8_t* container_dev, const void* info2,
+                               const void* syms_dev, const uint64_t* sym_off_dev,
+                               uint64_t* first_bad_host);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@ from .model_build import build_wide_model, histogram_wide, ideal_bits_wide  # no
 from .model_build import (cluster_contexts, fit_order1_set, histogram_pairs,  # noqa: F401
                           ideal_bits_order1)
 from . import container  # noqa: F401
-from .container import ContainerError, compress, decompress  # noqa: F401
+from .container import (ChecksumError, ContainerError, checksum_batch, compress,  # noqa: F401
+                        decompress)
 
 __version__ = "0.1.0"

@@ -43,6 +43,8 @@ EXPORTS = (
     "rc_histogram_order1",
     "rc_histogram_wide", "rc_ideal_bits_wide",
     "rc_histogram_pairs", "rc_cluster_contexts", "rc_ideal_bits_order1",
+    "rc_checksum_batch", "rc_container2_info_parse", "rc_container2_pack",
+    "rc_container2_offsets", "rc_container2_model", "rc_container2_verify",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
@@ -59,6 +61,15 @@ class ContainerInfo(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("n_chunks", "n_syms", "payload_bytes", "table_off",
                                               "index_off", "payload_off", "container_bytes")]
 Q_ALL_SYMBOLS = 1
+RC_E_CHECKSUM = -9
+CONTAINER2_F_CHECKSUMS = 1  # RC_CONTAINER2_F_CHECKSUMS
+
+
+class Container2Info(ctypes.Structure):
+    """rc_container2_info (include/range_coder.h): rc_container_info's fields, then RCB2's."""
+    _fields_ = ContainerInfo._fields_ + \
+               [(n, ctypes.c_uint32) for n in ("n_models", "first_row", "flags", "sym_bytes")] + \
+               [("sum_off", ctypes.c_uint64)]
 
 
 class StreamState(ctypes.Structure):
@@ -175,11 +186,28 @@ def load():
         L.rc_cluster_contexts.argtypes = [_P, _P, _U32, _U32, _P, ctypes.POINTER(_U32),
                                           ctypes.POINTER(_U32), ctypes.POINTER(ctypes.c_double)]
         L.rc_ideal_bits_order1.argtypes = [_P, _P, _P, _P, _U32, _P]
+    # RCB2 (a library of an earlier revision has none of these either)
+    c2 = ("rc_checksum_batch", "rc_container2_info_parse", "rc_container2_pack",
+          "rc_container2_offsets", "rc_container2_model", "rc_container2_verify")
+    old2 = not hasattr(L, c2[0])
+    if not old2:
+        C2P = ctypes.POINTER(Container2Info)
+        L.rc_checksum_batch.argtypes = [_P, _P, _P, _U32, _U32, _P]
+        L.rc_container2_info_parse.argtypes = [_P, _U64, C2P]
+        L.rc_container2_pack.argtypes = [_P, _P, _P, _P, _P, _P, _U32, _P, _P, _U64,
+                                         ctypes.POINTER(_U64)]
+        L.rc_container2_offsets.argtypes = [_P, _P, C2P, _P, _P, _P]
+        L.rc_container2_model.argtypes = [_P, _P, C2P, ctypes.POINTER(_P)]
+        L.rc_container2_verify.argtypes = [_P, _P, C2P, _P, _P, ctypes.POINTER(_U64)]
+        # host-only hook: rc_checksum_batch with a given grid (tests/test_gpu_container2.py)
+        L.rc_checksum_batch_grid_.argtypes = [_P, _P, _P, _U32, _U32, _P, _U32]
+        L.rc_checksum_batch_grid_.restype = _I
     # host-only hook of the wide histogram (not in the header; tests/test_gpu_wide_build.py)
     L.rc_histogram_wide_copies_.argtypes = [_U32]
     L.rc_histogram_wide_copies_.restype = _U32
     for name in EXPORTS:
-        if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit):
+        if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit) \
+                and not (old2 and name in c2):
             getattr(L, name).restype = _I
     _lib = L
     return L

@@ -382,6 +382,7 @@ const char* rc_status_string(rc_status s) {
     case RC_E_BAD_CONTAINER: return "malformed container";
     case RC_E_CAPACITY: return "destination too small";
     case RC_E_BAD_SYMBOL: return "symbol outside the alphabet";
+    case RC_E_CHECKSUM: return "checksum mismatch";
     default: return "unknown status";
   }
 }
