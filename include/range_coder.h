@@ -244,6 +244,30 @@ rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_
                                      const uint32_t* cum_freq_host, /* likewise */
                                      uint32_t total_freq, const uint8_t* ctx_map_host,
                                      uint32_t first_row, rc_model** out);
+/* An order-1 set with a period: the position in a record joins the context.  Tensors are mostly
+ * records of 2, 4 or 8 bytes (fp32, bf16, int32 fields, RGBA), and which byte of its record a
+ * symbol is often says more about it than the byte before.  With period P in {1, 2, 4, 8}:
+ *   the row of symbol 0 of every chunk is first_row;
+ *   the row of symbol i > 0 is ctx_map[(i mod P) * n_symbols + sym[i-1]], i counted from the
+ *   chunk's first symbol.
+ * Everything else is rc_model_create_order1_set's: the same rules for the tables, the same
+ * coding of symbol i as encoder.encode(&models[row_i], sym[i]) / decoder.decode(&models[row_i]),
+ * bit-exactly.  A map whose slices do not depend on the previous symbol is a purely positional
+ * model; a map of P identical slices codes what the unphased set codes.
+ * ctx_map_host: period x n_symbols bytes, slice ph (the map of the symbols with i mod P = ph)
+ * at ctx_map_host + ph * n_symbols.  A period outside {1, 2, 4, 8} is RC_E_ARG (periods that do
+ * not divide 16 are not supported: the kernels' 16-symbol blocks rely on 16 = 0 mod P); a map
+ * entry or first_row >= n_models is RC_E_BAD_MODEL.
+ * The result is an order-1 set: rc_encode_batch_order1, rc_decode_batch_order1 and
+ * rc_ideal_bits_order1 take it as they are and dispatch on its period.  With period 1 it is the
+ * set rc_model_create_order1_set makes (same kernels, same bytes).  A set with period > 1 is
+ * refused (RC_E_ARG) by every other entry point that takes a model, rc_container2_pack included:
+ * RCB2 frames one map, so a container of it would silently drop the period.                  */
+rc_status rc_model_create_order1_set_periodic(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                              const uint32_t* c_freq_host,
+                                              const uint32_t* cum_freq_host, uint32_t total_freq,
+                                              uint32_t period, const uint8_t* ctx_map_host,
+                                              uint32_t first_row, rc_model** out);
 /* rc_encode_batch with the row chosen by the chunk's previous symbol.
  * flags_dev     RC_F_BAD_SYMBOL for a symbol >= n_symbols, RC_F_ZERO_FREQ against the row the
  *               context chose, RC_F_CAPACITY with the exact length in out_len, RC_F_TOO_LONG; the
@@ -483,6 +507,20 @@ rc_status rc_histogram_pairs(rc_ctx* ctx, const uint8_t* syms_dev, const uint64_
                              uint32_t n_chunks, uint64_t* pair_hist_dev,
                              uint64_t* first_hist_dev);
 
+/* rc_histogram_pairs with the position in a record as a third index: what the maps of a periodic
+ * order-1 set are fitted from, one slice per phase.  period: 1, 2, 4 or 8 (else RC_E_ARG).
+ * pair_hist_dev   NULL or period x 256 x 256 uint64: [ph][p][s] is increased by the number of
+ *                 positions i >= 1 of a chunk with i mod period = ph, sym[i-1] = p, sym[i] = s
+ *                 (i counted from the chunk's first symbol)
+ * first_hist_dev  as rc_histogram_pairs
+ * Chunk boundaries reset the context; counts are ADDED into the arrays and are exact for any
+ * data; with both results NULL the call does nothing (RC_OK).  Summed over ph the pair counts
+ * are rc_histogram_pairs'.  Every phase reads the symbols again, so the call takes about
+ * `period` times as long.  Device pointers; stream-ordered.                                 */
+rc_status rc_histogram_pairs_periodic(rc_ctx* ctx, uint32_t period, const uint8_t* syms_dev,
+                                      const uint64_t* sym_off_dev, uint32_t n_chunks,
+                                      uint64_t* pair_hist_dev, uint64_t* first_hist_dev);
+
 /* Pair counts -> a context map of at most max_models classes and a first_row (host only, no
  * device needed; deterministic): greedy agglomerative clustering under the empirical-entropy
  * cost(v) = sum over v_s > 0 of v_s * log2(sum(v) / v_s), in f64.
@@ -509,7 +547,8 @@ rc_status rc_cluster_contexts(const uint64_t* pair_hist_host, const uint64_t* fi
 /* Batched ideal code length under an order-1 set, straight from the symbols:
  * bits_dev[k] = sum over the symbols i of chunk k of log2(total / c[row_i][sym_i]), f64, with
  * row_0 = first_row and row_i = ctx_map[sym[i-1]] as the order-1 coders pick them (after a
- * symbol >= n_symbols the next row is row 0, as they stage the map).  A term with c == 0 or a
+ * symbol >= n_symbols the next row is row 0, as they stage the map); for a periodic set
+ * row_i = ctx_map[(i mod P) * n_symbols + sym[i-1]], with the same sums.  A term with c == 0 or a
  * symbol >= n_symbols makes its chunk +inf; an empty chunk is 0.0; nothing is NaN.
  * `o1` must be an order-1 set of this context's device (RC_E_ARG for any other kind of model).
  * Stream-ordered; the call waits for the stream (it reads the set's rows back to price them on

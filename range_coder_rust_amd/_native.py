@@ -43,6 +43,7 @@ EXPORTS = (
     "rc_histogram_order1",
     "rc_histogram_wide", "rc_ideal_bits_wide",
     "rc_histogram_pairs", "rc_cluster_contexts", "rc_ideal_bits_order1",
+    "rc_model_create_order1_set_periodic", "rc_histogram_pairs_periodic",
     "rc_checksum_batch", "rc_container2_info_parse", "rc_container2_pack",
     "rc_container2_offsets", "rc_container2_model", "rc_container2_verify",
 )
@@ -175,6 +176,17 @@ def load():
     L.rc_model_order1_check_.restype = _I
     L.rc_model_order1_plan_.argtypes = [_U32, _U32, _P]
     L.rc_model_order1_plan_.restype = _I
+    # periodic order-1 sets (a library of an earlier revision has none of these)
+    per = ("rc_model_create_order1_set_periodic", "rc_histogram_pairs_periodic")
+    old3 = not hasattr(L, per[0])
+    if not old3:
+        L.rc_model_create_order1_set_periodic.argtypes = [_P, _U32, _U32, _P, _P, _U32, _U32, _P,
+                                                          _U32, ctypes.POINTER(_P)]
+        L.rc_histogram_pairs_periodic.argtypes = [_P, _U32, _P, _P, _U32, _P, _P]
+        L.rc_model_order1_check_periodic_.argtypes = [_U32, _U32, _P, _P, _U32, _U32, _P, _U32]
+        L.rc_model_order1_check_periodic_.restype = _I
+        L.rc_model_order1_plan_periodic_.argtypes = [_U32, _U32, _U32, _P]
+        L.rc_model_order1_plan_periodic_.restype = _I
     L.rc_histogram_wide.argtypes = [_P, _P, _P, _U32, _U32, _P, _P, _P]
     L.rc_ideal_bits_wide.argtypes = [_P, _P, _P, _P, _U32, _P]
     # fitting an order-1 set (a library of an earlier revision, tools/build_rev.sh, has none of
@@ -207,7 +219,7 @@ def load():
     L.rc_histogram_wide_copies_.restype = _U32
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit) \
-                and not (old2 and name in c2):
+                and not (old2 and name in c2) and not (old3 and name in per):
             getattr(L, name).restype = _I
     _lib = L
     return L

@@ -486,10 +486,16 @@ class Order1ModelSet:
 
     c_rows / cum_rows: K x n_symbols; ctx_map: at least n_symbols entries, each < K.  Rows, map
     and first_row are validated on the host at construction (ValueError); the device snapshot is
-    made on first use, so a set can be built and inspected without a device."""
+    made on first use, so a set can be built and inspected without a device.
+
+    period (1, 2, 4 or 8; rc_model_create_order1_set_periodic): the position in a record joins
+    the context.  ctx_map is then [period, n_symbols] and symbol i > 0 is coded with row
+    ctx_map[i % period, sym[i-1]], i counted from the chunk's start (for period 1 a flat map is
+    still accepted).  The order-1 batch calls and ideal_bits_order1 take such a set as they are;
+    a container cannot frame a period, so pack() and compress() raise for period > 1."""
 
     def __init__(self, c_rows, cum_rows=None, total_freq=None, ctx_map=None, first_row=0,
-                 ctx=None):
+                 ctx=None, period=1):
         c = np.ascontiguousarray(c_rows, dtype=np.uint32)
         if c.ndim != 2:
             raise ValueError("c_rows must be K x n_symbols")
@@ -507,9 +513,19 @@ class Order1ModelSet:
             raise ValueError("ctx_map is required: one row per previous symbol")
         cm = np.asarray(ctx_map)
         self.n_models, self.n_symbols = int(c.shape[0]), int(c.shape[1])
-        if cm.ndim != 1 or len(cm) < self.n_symbols:
+        period = int(period)
+        if period not in (1, 2, 4, 8):
+            raise ValueError("period must be 1, 2, 4 or 8")
+        if cm.ndim == 2 and cm.shape[0] == period and cm.shape[1] >= self.n_symbols:
+            cm = cm[:, :self.n_symbols].astype(np.int64)
+            if period == 1:
+                cm = cm[0]
+        elif period == 1 and cm.ndim == 1 and len(cm) >= self.n_symbols:
+            cm = cm[:self.n_symbols].astype(np.int64)
+        elif period == 1:
             raise ValueError(f"ctx_map needs {self.n_symbols} entries, one per symbol")
-        cm = cm[:self.n_symbols].astype(np.int64)
+        else:
+            raise ValueError(f"ctx_map must be [{period}, {self.n_symbols}]: one map per phase")
         first_row = int(first_row)
         if ((cm < 0) | (cm >= self.n_models)).any() or not 0 <= first_row < max(self.n_models, 1):
             raise ValueError(f"ctx_map entries and first_row must be rows of the set "
@@ -517,14 +533,15 @@ class Order1ModelSet:
         self.c, self.cum, self.total = c, cum, int(total_freq)
         self.ctx_map = np.ascontiguousarray(cm, dtype=np.uint8)
         self.first_row = first_row
+        self.period = period
         self._ctx = ctx
         self._handle = None
-        rc = N.load().rc_model_order1_check_(self.n_models, self.n_symbols,
-                                             ctypes.c_void_p(c.ctypes.data),
-                                             ctypes.c_void_p(cum.ctypes.data),
-                                             ctypes.c_uint32(self.total & 0xFFFFFFFF),
-                                             ctypes.c_void_p(self.ctx_map.ctypes.data),
-                                             ctypes.c_uint32(self.first_row))
+        tables = (self.n_models, self.n_symbols, ctypes.c_void_p(c.ctypes.data),
+                  ctypes.c_void_p(cum.ctypes.data), ctypes.c_uint32(self.total & 0xFFFFFFFF))
+        where = (ctypes.c_void_p(self.ctx_map.ctypes.data), ctypes.c_uint32(self.first_row))
+        # (period 1 goes through the calls it always did)
+        rc = (N.load().rc_model_order1_check_(*tables, *where) if period == 1 else
+              N.load().rc_model_order1_check_periodic_(*tables, ctypes.c_uint32(period), *where))
         if rc != N.RC_OK or self.total > 0xFFFFFFFF:
             raise ValueError(
                 f"order-1 set rejected: need 1..{N.MAX_SET_MODELS} rows of 1..256 symbols, one "
@@ -532,24 +549,25 @@ class Order1ModelSet:
                 "sum(c) == total_freq, and a ctx_map and first_row that name rows of the set")
 
     @classmethod
-    def from_counts(cls, count_rows, ctx_map, first_row=0, target_total=65536, ctx=None):
+    def from_counts(cls, count_rows, ctx_map, first_row=0, target_total=65536, ctx=None,
+                    period=1):
         """One row per context class from its histogram (rc_histogram_order1's rows), each scaled
         to target_total with every symbol kept encodable (rc_quantize_counts with
         RC_Q_ALL_SYMBOLS)."""
         from .model_build import quantize_counts
         rows = [quantize_counts(r, target_total, all_symbols=True) for r in count_rows]
         return cls([r[0] for r in rows], [r[1] for r in rows], int(target_total),
-                   ctx_map=ctx_map, first_row=first_row, ctx=ctx)
+                   ctx_map=ctx_map, first_row=first_row, ctx=ctx, period=period)
 
     def derive_indexes(self, syms):
         """The index stream the indexed calls would take for one chunk of symbols (host)."""
         s = _u8_chunk(syms)
         idx = np.empty(len(s), np.uint8)
         if len(s):
-            m = np.zeros(256, np.uint8)
-            m[:self.n_symbols] = self.ctx_map
+            m = np.zeros((self.period, 256), np.uint8)
+            m[:, :self.n_symbols] = self.ctx_map.reshape(self.period, self.n_symbols)
             idx[0] = self.first_row
-            idx[1:] = m[s[:-1]]
+            idx[1:] = m[np.arange(1, len(s)) % self.period, s[:-1]]
         return idx
 
     ctx = StaticModelSet.ctx
@@ -558,11 +576,18 @@ class Order1ModelSet:
     def handle(self):
         if self._handle is None:
             h = ctypes.c_void_p()
-            N.check(self.ctx._lib.rc_model_create_order1_set(
-                self.ctx.handle, self.n_models, self.n_symbols,
-                ctypes.c_void_p(self.c.ctypes.data), ctypes.c_void_p(self.cum.ctypes.data),
-                ctypes.c_uint32(self.total), ctypes.c_void_p(self.ctx_map.ctypes.data),
-                ctypes.c_uint32(self.first_row), ctypes.byref(h)), "rc_model_create_order1_set")
+            tables = (self.ctx.handle, self.n_models, self.n_symbols,
+                      ctypes.c_void_p(self.c.ctypes.data), ctypes.c_void_p(self.cum.ctypes.data),
+                      ctypes.c_uint32(self.total))
+            where = (ctypes.c_void_p(self.ctx_map.ctypes.data), ctypes.c_uint32(self.first_row),
+                     ctypes.byref(h))
+            if self.period == 1:
+                N.check(self.ctx._lib.rc_model_create_order1_set(*tables, *where),
+                        "rc_model_create_order1_set")
+            else:
+                N.check(self.ctx._lib.rc_model_create_order1_set_periodic(
+                    *tables, ctypes.c_uint32(self.period), *where),
+                    "rc_model_create_order1_set_periodic")
             self._handle = h
         return self._handle
 

@@ -88,10 +88,20 @@ def _pack2(model, slots, slot_off, code_len, sym_off, sums):
     return dst
 
 
+def _refuse_period(model):
+    """RCB2 frames one context map: a container of a periodic Order1ModelSet would silently drop
+    the period (rc_container2_pack returns RC_E_ARG for one), so it is refused before any work."""
+    if isinstance(model, Order1ModelSet) and model.period > 1:
+        raise ValueError(f"a container cannot frame an Order1ModelSet with period "
+                         f"{model.period}: keep the set beside the code, or use period 1")
+
+
 def pack(model, slots, slot_off, code_len, sym_off, sums=None, rcb2=False):
     """rc_container_pack: encoder slots -> a new container tensor (uint8, same device).  With
     checksums (sums, from checksum_batch), an Order1ModelSet or WideStaticModel, or rcb2=True,
-    the container is RCB2 (rc_container2_pack), else RCB1."""
+    the container is RCB2 (rc_container2_pack), else RCB1.  An Order1ModelSet with period > 1 is
+    a ValueError."""
+    _refuse_period(model)
     torch = _torch()
     _check_dev(slots, "slots", (torch.uint8,))
     for name, t in (("slot_off", slot_off), ("code_len", code_len), ("sym_off", sym_off)):
@@ -167,7 +177,7 @@ def _model_of2(container, inf, ctx):
         m = Order1ModelSet.__new__(Order1ModelSet)
         m.c, m.cum, m.n_models = c, cum, k
         m.ctx_map = tab[4 * k * n:4 * k * n + n].copy()
-        m.first_row = inf.first_row
+        m.first_row, m.period = inf.first_row, 1
     else:
         cls = StaticModel if inf.kind == 0 else WideStaticModel
         m = cls.__new__(cls)
@@ -241,11 +251,14 @@ def compress(data, chunk_size=65536, model=None, target_total=1 << 16, ctx=None,
                             (DESIGN.md §9.7); ask for more where size matters more than
                             decode speed.  Empty data has nothing to fit and is written with
                             the order-0 table (kind 0), as the order-0 path writes it.
-      model                 an Order1ModelSet or a WideStaticModel is used as given.
+      model                 an Order1ModelSet or a WideStaticModel is used as given (an
+                            Order1ModelSet with period > 1 is a ValueError: the container has
+                            no field for a period).
       uint16 / int16 data   16-bit symbols: model None builds a WideStaticModel over n_symbols
                             symbols (default: the data's largest symbol + 1; at most 4096).
       checksum=True         one checksum per chunk of the input (checksum_batch), which
                             decompress compares with the decoded symbols."""
+    _refuse_period(model)
     torch = _torch()
     wide = data.dtype != torch.uint8 or isinstance(model, WideStaticModel)
     if wide:

@@ -292,6 +292,9 @@ bool rc_model_is_order1_(const rc_model* m);
 bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int* device);
 // rc_kernels.hip: an order-1 set's cum rows (device memory: [n_models][257], cum[0 .. 256] with
 // the entries from n_symbols on holding the total), its staged 256-entry map (device memory),
-// first_row, sizes and device; false for any other kind of model (rc_ideal_bits_order1)
+// first_row, sizes and device; false for any other kind of model (rc_ideal_bits_order1).  A
+// periodic set's map is its `period` staged slices back to back.
 bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** map,
                            u32* first_row, u32* n_models, u32* n_symbols, int* device);
+// the period of an order-1 set (1, 2, 4 or 8); 0 for any other kind of model
+u32 rc_model_order1_period_(const rc_model* m);

@@ -12,6 +12,8 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
   histogram_order1(syms, sym_off, ctx_map, first_row)   rc_histogram_order1: symbol counts by
                                   context class, the previous symbol picking the class (HIP)
   build_order1_set(syms, sym_off, ctx_map)   those counts -> Order1ModelSet, in one call
+  histogram_pairs_periodic(syms, sym_off, P) rc_histogram_pairs_periodic: the pair histogram per
+                                  position in a record of P bytes (HIP)
   histogram_pairs(syms, sym_off)  rc_histogram_pairs: the full 256 x 256 pair histogram and the
                                   histogram of the chunks' first symbols (HIP)
   cluster_contexts(pair, first, K)           rc_cluster_contexts: those counts -> a context map
@@ -128,11 +130,43 @@ def histogram_order1(syms, sym_off, ctx_map, first_row=0, n_models=None, hist=No
     return hist
 
 
+def _ctx_maps256(ctx_map, period):
+    """[period, 256] uint8 from a [period, n] map (symbols past it: row 0)."""
+    cm = np.asarray(ctx_map)
+    if cm.ndim != 2 or cm.shape[0] != period:
+        raise ValueError(f"ctx_map must be [{period}, n]: one map per phase")
+    return np.stack([_ctx_map256(r) for r in cm])
+
+
+def _class_counts(pair, first, maps, first_row, n_models):
+    """The counts of the rows of a periodic set from periodic pair counts (host): row j collects
+    pair[ph][p] of every (ph, p) with maps[ph][p] == j, and first_row the first symbols."""
+    counts = np.zeros((n_models, 256), np.uint64)
+    for ph in range(len(pair)):
+        np.add.at(counts, maps[ph].astype(np.int64), pair[ph].astype(np.uint64))
+    counts[first_row] += first.astype(np.uint64)
+    return counts
+
+
 def build_order1_set(syms, sym_off, ctx_map, first_row=0, target_total=1 << 16, n_symbols=256,
-                     n_models=None, ctx=None):
+                     n_models=None, ctx=None, period=1):
     """Pair counts of the batch on the GPU, then an Order1ModelSet of the rows quantised from
-    them (every symbol kept encodable in every row)."""
+    them (every symbol kept encodable in every row).  period > 1: ctx_map is [period, n] and
+    the rows' counts are summed on the host from histogram_pairs_periodic's."""
     ctx = ctx or default_context(syms.device.index)
+    period = int(period)
+    if period != 1:
+        maps = _ctx_maps256(ctx_map, period)
+        K = int(n_models) if n_models is not None else max(int(maps.max()), int(first_row)) + 1
+        if not 1 <= K <= N.MAX_SET_MODELS or int(maps.max()) >= K or not 0 <= int(first_row) < K:
+            raise ValueError(f"ctx_map and first_row must name rows 0..{K - 1} of at most "
+                             f"{N.MAX_SET_MODELS}")
+        pair, first = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx)
+        counts = _class_counts(pair.cpu().numpy(), first.cpu().numpy(), maps, int(first_row), K)
+        if n_symbols < 256 and counts[:, n_symbols:].any():
+            raise ValueError(f"symbols >= {n_symbols} present")
+        return Order1ModelSet.from_counts(counts[:, :n_symbols], maps[:, :n_symbols], first_row,
+                                          target_total, ctx=ctx, period=period)
     hist = histogram_order1(syms, sym_off, ctx_map, first_row, n_models=n_models, ctx=ctx)
     counts = hist.cpu().numpy().astype(np.uint64)
     if n_symbols < 256 and counts[:, n_symbols:].any():
@@ -167,6 +201,38 @@ def histogram_pairs(syms, sym_off, pair_hist=None, first_hist=None, ctx=None):
     return pair_hist, first_hist
 
 
+def histogram_pairs_periodic(syms, sym_off, period, pair_hist=None, first_hist=None, ctx=None):
+    """rc_histogram_pairs_periodic on torch tensors (async, torch's current stream).
+
+    Returns (pair_hist, first_hist): int64[period, 256, 256], [ph][p][s] = the positions i >= 1
+    of a chunk with i % period == ph, sym[i-1] = p and sym[i] = s (i counted from the chunk's
+    start), and int64[256] as histogram_pairs gives it.  Chunk boundaries reset the context.
+    Given arrays are added into.  period: 1, 2, 4 or 8."""
+    torch = _torch()
+    _check_dev(syms, "syms", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    period = int(period)
+    if period not in (1, 2, 4, 8):
+        raise ValueError("period must be 1, 2, 4 or 8")
+    ctx = ctx or default_context(syms.device.index)
+    n = sym_off.numel() - 1
+    for name, t, shape in (("pair_hist", pair_hist, (period, 256, 256)),
+                           ("first_hist", first_hist, (256,))):
+        if t is not None:
+            _check_dev(t, name, (torch.int64, torch.uint64))
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {list(shape)}")
+    if pair_hist is None:
+        pair_hist = torch.zeros((period, 256, 256), dtype=torch.int64, device=syms.device)
+    if first_hist is None:
+        first_hist = torch.zeros(256, dtype=torch.int64, device=syms.device)
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_histogram_pairs_periodic(ctx.handle, period, _ptr(syms), _ptr(sym_off),
+                                                 n, _ptr(pair_hist), _ptr(first_hist)),
+            "rc_histogram_pairs_periodic")
+    return pair_hist, first_hist
+
+
 def cluster_contexts(pair_hist, first_hist, n_models=64, n_symbols=256):
     """rc_cluster_contexts (host): pair counts [256, 256] and first-symbol counts [256] -> a
     context map of at most n_models classes, by greedy agglomerative clustering under the
@@ -195,12 +261,44 @@ def cluster_contexts(pair_hist, first_hist, n_models=64, n_symbols=256):
     return cm[:int(n_symbols)], int(first_row.value), int(k.value), float(cost.value)
 
 
-def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=256, ctx=None):
+def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=256, ctx=None,
+                   period=1):
     """An Order1ModelSet fitted to the batch: pair counts on the GPU (histogram_pairs), a context
     map of at most n_models classes from them (cluster_contexts), the classes' counts on the GPU
     (histogram_order1 with the map found) and their quantised rows.  The set's ctx_map and
-    first_row are the ones found; it has as many rows as classes were found."""
+    first_row are the ones found; it has as many rows as classes were found.
+
+    period > 1 (2, 4 or 8) fits a periodic set: periodic pair counts on the GPU
+    (histogram_pairs_periodic), then cluster_contexts once per phase with n_models // period
+    classes (phase 0 gets the start-of-chunk counts as its pseudo-context, the others none;
+    ValueError if n_models < period), phase ph's rows numbered after those of the phases before
+    it, the classes' counts summed on the host from the pair counts (no second pass over the
+    symbols) and the rows quantised.  That is `period` runs of the host clustering, about 0.17 s
+    each, and the phases cannot share a row: every phase gets the same number
+    of classes whether it needs them or not."""
+    period = int(period)
+    if period not in (1, 2, 4, 8):
+        raise ValueError("period must be 1, 2, 4 or 8")
+    if int(n_models) < period:
+        raise ValueError(f"n_models = {n_models} leaves a phase of period {period} no row")
     ctx = ctx or default_context(syms.device.index)
+    if period != 1:
+        pair_t, first_t = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx)
+        pair, first = pair_t.cpu().numpy(), first_t.cpu().numpy()
+        maps = np.zeros((period, 256), np.uint8)
+        first_row, rows = 0, 0
+        for ph in range(period):
+            if ph and not pair[ph].any():
+                continue  # (no chunk reaches this phase: its map is never read, row 0 will do)
+            cm, fr, k, _ = cluster_contexts(pair[ph], first if ph == 0 else np.zeros(256),
+                                            int(n_models) // period, n_symbols)
+            maps[ph, :len(cm)] = cm + rows
+            if ph == 0:
+                first_row = fr
+            rows += k
+        counts = _class_counts(pair, first, maps, first_row, rows)
+        return Order1ModelSet.from_counts(counts[:, :n_symbols], maps[:, :n_symbols], first_row,
+                                          target_total, ctx=ctx, period=period)
     pair, first = histogram_pairs(syms, sym_off, ctx=ctx)
     cm, first_row, k, _ = cluster_contexts(pair.cpu().numpy(), first.cpu().numpy(), n_models,
                                            n_symbols)
