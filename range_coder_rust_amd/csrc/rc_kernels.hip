@@ -107,9 +107,7 @@ struct rc_model {
   SetPlan plan;
   WideArgs wide;
   WidePlan wplan;
-  O1Args o1;
-  O1PArgs o1p;  // kind 4 with o1_period > 1 (then `o1` is unused)
-  u32 o1_period;  // kind 4: 1, 2, 4 or 8
+  O1Args o1;  // kind 4 (o1.period: 1, 2, 4 or 8)
   int device;
   int div;
   ModelArgs args;
@@ -133,18 +131,16 @@ bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int*
 bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** map,
                            u32* first_row, u32* n_models, u32* n_symbols, int* device) {
   if (!m || m->kind != RC_KIND_ORDER1) return false;
-  const bool per = m->o1_period > 1;
-  const SetArgs& s = per ? m->o1p.s : m->o1.s;
-  *rows = s.rows;
-  *map = per ? m->o1p.map : m->o1.map;
-  *first_row = per ? m->o1p.first_row : m->o1.first_row;
-  *n_models = s.k;
-  *n_symbols = s.m.n;
+  *rows = m->o1.s.rows;
+  *map = m->o1.map;
+  *first_row = m->o1.first_row;
+  *n_models = m->o1.s.k;
+  *n_symbols = m->o1.s.m.n;
   *device = m->device;
   return true;
 }
 u32 rc_model_order1_period_(const rc_model* m) {
-  return m && m->kind == RC_KIND_ORDER1 ? m->o1_period : 0u;
+  return m && m->kind == RC_KIND_ORDER1 ? m->o1.period : 0u;
 }
 
 namespace {
@@ -759,8 +755,7 @@ rc_status rc_model_set_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* o
                             [&](SetPlan* p) { rc_set_plan(n_models, total_freq, p); });
 }
 
-// The device snapshot of a checked set for `plan` (rc_set_plan's, or rc_order1_plan_periodic's
-// with maps: the period x 256 context-map bytes of an order-1 set, kept behind the tables)
+// The device snapshot of a checked set for `plan` (rc_set_plan's, or rc_order1_plan's with maps: the period x 256 context-map bytes of an order-1 set, kept behind the tables)
 static rc_status set_build(rc_ctx* ctx, int kind, uint32_t n_models, uint32_t n_symbols,
                            const uint32_t* c_freq, const uint32_t* cum_freq, uint32_t total_freq,
                            const SetPlan& plan, const uint8_t* maps, uint32_t period,
@@ -797,23 +792,16 @@ static rc_status set_build(rc_ctx* ctx, int kind, uint32_t n_models, uint32_t n_
       &d);
   if (up != RC_OK) return up;
   mm->plan = plan;
-  SetArgs& a = kind != RC_KIND_ORDER1 ? mm->set : period > 1 ? mm->o1p.s : mm->o1.s;
+  SetArgs& a = kind != RC_KIND_ORDER1 ? mm->set : mm->o1.s;
   small_model_args(a.m, n_symbols, total_freq, plan.dec_bits, plan.dec_shift);
   a.rows = (const u32*)d;
   a.lut = (const u32*)(d + row_bytes);
   a.k = n_models;
   a.tab_bytes = plan.enc_tab;
   if (kind == RC_KIND_ORDER1) {
-    const uint8_t* dmap = (const uint8_t*)(d + row_bytes + lut_bytes);
-    mm->o1_period = period;
-    if (period > 1) {
-      mm->o1p.map = dmap;
-      mm->o1p.first_row = first_row;
-      mm->o1p.period = period;
-    } else {
-      mm->o1.map = dmap;
-      mm->o1.first_row = first_row;
-    }
+    mm->o1.map = (const uint8_t*)(d + row_bytes + lut_bytes);
+    mm->o1.first_row = first_row;
+    mm->o1.period = period;
   }
   *out = mm;
   return RC_OK;
@@ -883,7 +871,7 @@ rc_status rc_model_order1_check_(uint32_t n_models, uint32_t n_symbols, const ui
 // map; the encoder's numbers are the set's).
 rc_status rc_model_order1_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* out) {
   return plan_hook<SetPlan>(n_models >= 1 && n_models <= RC_MAX_SET_MODELS, total_freq, out,
-                            [&](SetPlan* p) { rc_order1_plan(n_models, total_freq, p); });
+                            [&](SetPlan* p) { rc_order1_plan(n_models, total_freq, 1, p); });
 }
 
 rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
@@ -896,7 +884,7 @@ rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_
       order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, ctx_map, first_row);
   if (ok != RC_OK) return ok;
   SetPlan plan;
-  rc_order1_plan(n_models, total_freq, &plan);
+  rc_order1_plan(n_models, total_freq, 1, &plan);
   // the kernels stage 256 entries: a symbol past the alphabet (a flagged chunk) maps to row 0
   uint8_t map256[256] = {0};
   memcpy(map256, ctx_map, n_symbols);
@@ -932,7 +920,7 @@ rc_status rc_model_order1_plan_periodic_(uint32_t n_models, uint32_t total_freq,
   if (!o1_period_ok(period)) return RC_E_ARG;
   return plan_hook<SetPlan>(
       n_models >= 1 && n_models <= RC_MAX_SET_MODELS, total_freq, out,
-      [&](SetPlan* p) { rc_order1_plan_periodic(n_models, total_freq, period, p); });
+      [&](SetPlan* p) { rc_order1_plan(n_models, total_freq, period, p); });
 }
 
 rc_status rc_model_create_order1_set_periodic(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
@@ -951,7 +939,7 @@ rc_status rc_model_create_order1_set_periodic(rc_ctx* ctx, uint32_t n_models, ui
                                              period, ctx_map, first_row);
   if (ok != RC_OK) return ok;
   SetPlan plan;
-  rc_order1_plan_periodic(n_models, total_freq, period, &plan);
+  rc_order1_plan(n_models, total_freq, period, &plan);
   // the kernels stage 256 entries per slice: a symbol past the alphabet maps to row 0
   uint8_t maps[O1_MAX_PERIOD * 256] = {0};
   for (u32 ph = 0; ph < period; ++ph)
@@ -966,10 +954,6 @@ rc_status rc_encode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t*
   return batch_call(ctx, o1, 1u << RC_KIND_ORDER1, true, n_chunks,
                     syms && sym_off && out && out_off && out_len && flags,
                     "order-1 encode launch", [&] {
-                      if (o1->o1_period > 1)
-                        return rc_order1_encode_launch_periodic(
-                            ctx->cur, ctx->knobs, o1->o1p, o1->div, o1->plan, syms, sym_off,
-                            n_chunks, out, out_off, out_len, flags);
                       return rc_order1_encode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div,
                                                      o1->plan, syms, sym_off, n_chunks, out,
                                                      out_off, out_len, flags);
@@ -983,10 +967,6 @@ rc_status rc_decode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t*
   return batch_call(ctx, o1, 1u << RC_KIND_ORDER1, true, n_chunks,
                     code && code_off && code_len && syms_out && sym_off && flags,
                     "order-1 decode launch", [&] {
-                      if (o1->o1_period > 1)
-                        return rc_order1_decode_launch_periodic(
-                            ctx->cur, ctx->knobs, o1->o1p, o1->div, o1->plan, code, code_off,
-                            code_len, syms_out, sym_off, n_chunks, flags);
                       return rc_order1_decode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div,
                                                      o1->plan, code, code_off, code_len, syms_out,
                                                      sym_off, n_chunks, flags);

@@ -250,6 +250,17 @@ __global__ __launch_bounds__(256) void k_histogram_order1(
 // No counter can wrap: every symbol counted adds one to at most one counter of its workgroup,
 // and the counters are flushed into the u64 results before the workgroup has counted 2^32
 // symbols since the last flush, so none exceeds 2^32 - 1 whatever the data.
+//
+// PER (rc_histogram_pairs_periodic; periodic order-1 sets, rc_order1.h): the position in a record
+// is a third index, pair[ph][p][s] counts the positions i >= 1 of a chunk with i mod P = ph,
+// sym[i-1] = p and sym[i] = s.  The same structure with O1P_SLICES * P slices, (phase, part of
+// the contexts): workgroup b belongs to slice g = b % (O1P_SLICES * P), phase g / O1P_SLICES and
+// contexts [(g % O1P_SLICES) R, (g % O1P_SLICES + 1) R).  A lane's 16 consecutive symbols start
+// at a multiple of 16 from the chunk's start (the segments are multiples of 16 too), so its j-th
+// symbol has phase j mod P whatever the lane: the phase test is a compare of two wave-uniform
+// values per unrolled j.  Every slice reads and unpacks every symbol, and the budget counts every
+// symbol read, more than the slice counts.  Without PER, `period` is not read (P = 1: the phase
+// test is always true and compiles away).
 #ifndef O1P_SLICES       // (scratch builds: -DO1P_SLICES=n -DO1P_WG=lanes)
 #define O1P_SLICES 2u
 #endif
@@ -265,14 +276,18 @@ __global__ __launch_bounds__(256) void k_histogram_order1(
 #define O1P_WORDS (O1P_ROWS * 256u + 256u)        // the slice's counters, then the first symbols'
 #define O1P_LDS (4u * O1P_WORDS)
 
+template <bool PER>
 __global__ __launch_bounds__(O1P_WG) void k_histogram_pairs(
     const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
-    u64* __restrict__ pair, u64* __restrict__ first) {
+    u64* __restrict__ pair, u64* __restrict__ first, u32 period) {
   extern __shared__ u32 s_pp[];
   const u32 tid = threadIdx.x;
-  const u32 g = blockIdx.x % O1P_SLICES, w = blockIdx.x / O1P_SLICES;
-  const u32 G = gridDim.x / O1P_SLICES;
-  const u32 base = g * O1P_ROWS;  // the slice's first context
+  const u32 P = PER ? period : 1u, pm = P - 1;
+  const u32 slices = O1P_SLICES * P;
+  const u32 g = blockIdx.x % slices, w = blockIdx.x / slices;
+  const u32 G = gridDim.x / slices;
+  const u32 ph = g / O1P_SLICES;
+  const u32 base = (g % O1P_SLICES) * O1P_ROWS;  // the slice's first context
   const bool do_first = first && g == 0;
   RC_VGPR_FLOOR_48();
   if (!pair && !do_first) return;  // (workgroup-uniform)
@@ -285,7 +300,7 @@ __global__ __launch_bounds__(O1P_WG) void k_histogram_pairs(
       for (u32 j = tid; j < O1P_ROWS * 256u; j += O1P_WG) {
         const u32 v = s_pp[j];
         if (v) {
-          atomicAdd(reinterpret_cast<unsigned long long*>(pair + base * 256u + j),
+          atomicAdd(reinterpret_cast<unsigned long long*>(pair + ((u64)ph * 256u + base) * 256u + j),
                     (unsigned long long)v);
           s_pp[j] = 0;
         }
@@ -344,109 +359,6 @@ __global__ __launch_bounds__(O1P_WG) void k_histogram_pairs(
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const u32 s = (ws[q] >> (8 * j)) & 255u;
-              if (rel < O1P_ROWS) atomicAdd(&s_pp[rel * 256u + s], 1u);
-              rel = s - base;
-            }
-          }
-        } else {
-          for (u64 j = i; j < b1; ++j) {
-            const u32 s = p[j];
-            if (rel < O1P_ROWS) atomicAdd(&s_pp[rel * 256u + s], 1u);
-            rel = s - base;
-          }
-        }
-      }
-    }
-  }
-  flush();
-}
-
-// k_histogram_pairs_periodic: k_histogram_pairs with the position in a record as a third index
-// (periodic order-1 sets, rc_order1.h): pair[ph][p][s] counts the positions i >= 1 of a chunk with
-// i mod P = ph, sym[i-1] = p and sym[i] = s.  The same structure with 2 P slices, (phase, half of
-// the contexts): workgroup b belongs to slice g = b % (2 P), phase g / 2 and contexts
-// [(g & 1) R, ((g & 1) + 1) R).  A lane's 16 consecutive symbols start at a multiple of 16 from
-// the chunk's start (the segments are multiples of 16 too), so its j-th symbol has phase j mod P
-// whatever the lane: the phase test is a compare of two wave-uniform values per unrolled j.
-// Every slice reads and unpacks every symbol, as there.  The overflow rule is k_histogram_pairs':
-// the budget counts every symbol read, more than the slice counts, and the counters are flushed
-// before a workgroup has read 2^32 symbols since the last flush.
-__global__ __launch_bounds__(O1P_WG) void k_histogram_pairs_periodic(
-    u32 P, const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
-    u64* __restrict__ pair, u64* __restrict__ first) {
-  extern __shared__ u32 s_pp[];
-  const u32 tid = threadIdx.x;
-  const u32 slices = 2u * P, pm = P - 1;
-  const u32 g = blockIdx.x % slices, w = blockIdx.x / slices;
-  const u32 G = gridDim.x / slices;
-  const u32 ph = g >> 1;
-  const u32 base = (g & 1u) * O1P_ROWS;  // the slice's first context
-  const bool do_first = first && g == 0;
-  RC_VGPR_FLOOR_48();
-  if (!pair && !do_first) return;  // (workgroup-uniform)
-  u32* const s_first = s_pp + O1P_ROWS * 256u;
-  for (u32 j = tid; j < O1P_WORDS; j += O1P_WG) s_pp[j] = 0;
-  __syncthreads();
-  auto flush = [&]() {
-    __syncthreads();
-    if (pair) {
-      for (u32 j = tid; j < O1P_ROWS * 256u; j += O1P_WG) {
-        const u32 v = s_pp[j];
-        if (v) {
-          atomicAdd(reinterpret_cast<unsigned long long*>(pair + ((u64)ph * 256u + base) * 256u + j),
-                    (unsigned long long)v);
-          s_pp[j] = 0;
-        }
-      }
-    }
-    if (do_first && tid < 256) {
-      const u32 v = s_first[tid];
-      if (v) {
-        atomicAdd(reinterpret_cast<unsigned long long*>(first + tid), (unsigned long long)v);
-        s_first[tid] = 0;
-      }
-    }
-    __syncthreads();
-  };
-  u64 pending = 0;  // symbols read since the last flush (workgroup-uniform)
-  const u32 sub = tid / O1P_SUB, t = tid % O1P_SUB;
-  for (u32 k0 = w * O1P_Q; k0 < n_chunks; k0 += G * O1P_Q) {
-    u64 len[O1P_Q], nmax = 0;
-#pragma unroll
-    for (u32 q = 0; q < O1P_Q; ++q) {
-      len[q] = k0 + q < n_chunks ? sym_off[k0 + q + 1] - sym_off[k0 + q] : 0;
-      nmax = len[q] > nmax ? len[q] : nmax;
-    }
-    const u32 k = k0 + sub;
-    const u64 s0 = k < n_chunks ? sym_off[k] : 0, n = k < n_chunks ? sym_off[k + 1] - s0 : 0;
-    const uint8_t* p = syms + s0;
-    for (u64 b0 = 0; b0 < nmax; b0 += O1P_SEG) {
-      u64 cnt = 0;  // at most O1P_Q * O1P_SEG = 2^31
-#pragma unroll
-      for (u32 q = 0; q < O1P_Q; ++q)
-        cnt += len[q] > b0 ? (len[q] - b0 < O1P_SEG ? len[q] - b0 : O1P_SEG) : 0;
-      if (pending + cnt > 0xFFFFFFFFull) {
-        flush();
-        pending = 0;
-      }
-      pending += cnt;
-      if (b0 >= n) continue;
-      const u64 b1 = n - b0 < O1P_SEG ? n : b0 + O1P_SEG;
-      if (!pair) {  // first symbols only
-        if (b0 == 0 && t == 0) atomicAdd(&s_first[p[0]], 1u);
-        continue;
-      }
-      for (u64 i = b0 + 16ull * t; i < b1; i += 16ull * O1P_SUB) {
-        u32 rel = i ? (u32)p[i - 1] - base : 0x80000000u;
-        if (i == 0 && do_first) atomicAdd(&s_first[p[0]], 1u);
-        if (i + 16 <= b1) {
-          const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
-          const u32 ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const u32 s = (ws[q] >> (8 * j)) & 255u;
               if (((u32)(4 * q + j) & pm) == ph && rel < O1P_ROWS)
                 atomicAdd(&s_pp[rel * 256u + s], 1u);
               rel = s - base;
@@ -479,16 +391,28 @@ __global__ __launch_bounds__(O1P_WG) void k_histogram_pairs_periodic(
 // 16 ceil(n_k / 1024) <= n_k / 64 + 16 non-negative terms one by one and the butterfly adds
 // log2 64 = 6 more steps, so the relative error of a finite chunk of n_k symbols is at most
 // about (n_k / 64 + 22) * 2^-53: below 1e-12 up to n_k = 5.7e5.
+//
+// PER (a periodic set, rc_order1.h): row_i = map[i mod P][sym[i-1]].  The lanes start at multiples
+// of 16 from the chunk's start, so the symbol after a lane's j-th has phase (j + 1) mod P and the
+// byte before its first pairs with phase 0: only the staged map (P x 256 B) and its index change;
+// the sums, their order and so the accuracy bound are the same.  Without PER, `period` is not
+// read (P = 1: every map index is the symbol).
+template <bool PER>
 __global__ __launch_bounds__(1024) void k_ideal_bits_order1(
     const double* __restrict__ icl, const uint8_t* __restrict__ map, u32 first_row, u32 K,
     const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
-    double* __restrict__ bits) {
+    double* __restrict__ bits, u32 period) {
   extern __shared__ double s_o1i[];
   uint8_t* const s_map = reinterpret_cast<uint8_t*>(s_o1i + K * 256u);
-  const u32 lane = threadIdx.x & 63, waves = blockDim.x >> 6;
+  const u32 lane = threadIdx.x & 63, waves = blockDim.x >> 6, pm = PER ? period - 1 : 0u;
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   for (u32 j = threadIdx.x; j < K * 256u; j += blockDim.x) s_o1i[j] = icl[j];
-  if (threadIdx.x < 256) s_map[threadIdx.x] = map[threadIdx.x];
+  // (one map: a workgroup has 256 lanes or more)
+  if (PER) {
+    for (u32 j = threadIdx.x; j < period * 256u; j += blockDim.x) s_map[j] = map[j];
+  } else if (threadIdx.x < 256) {
+    s_map[threadIdx.x] = map[threadIdx.x];
+  }
   __syncthreads();
   const u32 nw = gridDim.x * waves;
   for (u32 k = blockIdx.x * waves + wave; k < n_chunks; k += nw) {
@@ -497,59 +421,6 @@ __global__ __launch_bounds__(1024) void k_ideal_bits_order1(
     double acc = 0.0;
     for (u64 i = 16ull * lane; i < n; i += 16ull * 64) {
       u32 row = i ? (u32)s_map[p[i - 1]] : first_row;  // chunk boundaries reset the context
-      if (i + 16 <= n) {
-        const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
-        const u32 ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const u32 s = (ws[q] >> (8 * j)) & 255u;
-            acc += s_o1i[row * 256u + s];
-            row = s_map[s];
-          }
-        }
-      } else {
-        for (u64 j = i; j < n; ++j) {
-          const u32 s = p[j];
-          acc += s_o1i[row * 256u + s];
-          row = s_map[s];
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-      const u64 x = (u64)__double_as_longlong(acc);
-      const u64 y = ((u64)(u32)__shfl_xor((int)hi32(x), o) << 32) | (u32)__shfl_xor((int)(u32)x, o);
-      acc += __longlong_as_double((long long)y);
-    }
-    if (lane == 0) bits[k] = acc;
-  }
-}
-
-// k_ideal_bits_o1p: k_ideal_bits_order1 for a periodic set (rc_order1.h), row_i =
-// map[i mod P][sym[i-1]].  The lanes start at multiples of 16 from the chunk's start, so the
-// symbol after a lane's j-th has phase (j + 1) mod P and the byte before its first pairs with
-// phase 0: only the staged map (P x 256 B) and its index change; the sums, their order and so the
-// accuracy bound are k_ideal_bits_order1's.
-__global__ __launch_bounds__(1024) void k_ideal_bits_o1p(
-    const double* __restrict__ icl, const uint8_t* __restrict__ map, u32 P, u32 first_row, u32 K,
-    const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
-    double* __restrict__ bits) {
-  extern __shared__ double s_o1i[];
-  uint8_t* const s_map = reinterpret_cast<uint8_t*>(s_o1i + K * 256u);
-  const u32 lane = threadIdx.x & 63, waves = blockDim.x >> 6, pm = P - 1;
-  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (u32 j = threadIdx.x; j < K * 256u; j += blockDim.x) s_o1i[j] = icl[j];
-  for (u32 j = threadIdx.x; j < P * 256u; j += blockDim.x) s_map[j] = map[j];
-  __syncthreads();
-  const u32 nw = gridDim.x * waves;
-  for (u32 k = blockIdx.x * waves + wave; k < n_chunks; k += nw) {
-    const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
-    const uint8_t* p = syms + s0;
-    double acc = 0.0;
-    for (u64 i = 16ull * lane; i < n; i += 16ull * 64) {
-      u32 row = i ? (u32)s_map[p[i - 1]] : first_row;  // (i mod P = 0: slice 0)
       if (i + 16 <= n) {
         const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
         const u32 ws[4] = {v.x, v.y, v.z, v.w};
@@ -829,6 +700,36 @@ struct DevSet {
 };
 }  // namespace
 
+// rc_histogram_pairs (PER = false, period 1) and rc_histogram_pairs_periodic (PER = true, period
+// 1 included): each call keeps its own instantiation of the kernel
+template <bool PER>
+static rc_status histogram_pairs(rc_ctx* ctx, u32 period, const uint8_t* syms,
+                                 const uint64_t* sym_off, uint32_t n_chunks, uint64_t* pair_hist,
+                                 uint64_t* first_hist) {
+  hipStream_t s;
+  int dev;
+  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (period != 1 && period != 2 && period != 4 && period != 8) return RC_E_ARG;
+  if (n_chunks == 0 || (!pair_hist && !first_hist)) return RC_OK;
+  if (!syms || !sym_off) return RC_E_ARG;
+  DevSet g(dev);
+  rc_svc_yield_all_();
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return RC_E_DEVICE;
+  if (set_allow_lds(reinterpret_cast<const void*>(k_histogram_pairs<PER>)) != hipSuccess)
+    return RC_E_DEVICE;
+  // as many workgroups as the CUs hold (their LDS and 32 waves each), in O1P_SLICES * P groups
+  // that stride over the chunks side by side
+  const u32 slices = O1P_SLICES * period;
+  const u32 per_cu = std::max(1u, std::min(163840u / O1P_LDS, 2048u / O1P_WG));
+  const u32 groups =
+      std::max(1u, std::min<u32>((n_chunks + O1P_Q - 1) / O1P_Q, (u32)cus * per_cu / slices));
+  hipLaunchKernelGGL(k_histogram_pairs<PER>, dim3(groups * slices), dim3(O1P_WG), O1P_LDS, s, syms,
+                     sym_off, n_chunks, pair_hist, first_hist, period);
+  return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+}
+
 extern "C" {
 
 rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms, const uint64_t* sym_off,
@@ -885,52 +786,13 @@ rc_status rc_histogram_order1(rc_ctx* ctx, uint32_t n_models, const uint8_t* ctx
 
 rc_status rc_histogram_pairs(rc_ctx* ctx, const uint8_t* syms, const uint64_t* sym_off,
                              uint32_t n_chunks, uint64_t* pair_hist, uint64_t* first_hist) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (n_chunks == 0 || (!pair_hist && !first_hist)) return RC_OK;
-  if (!syms || !sym_off) return RC_E_ARG;
-  DevSet g(dev);
-  rc_svc_yield_all_();
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return RC_E_DEVICE;
-  if (set_allow_lds(reinterpret_cast<const void*>(k_histogram_pairs)) != hipSuccess)
-    return RC_E_DEVICE;
-  // as many workgroups as the CUs hold (their LDS and 32 waves each), in O1P_SLICES groups that
-  // stride over the chunks side by side
-  const u32 per_cu = std::max(1u, std::min(163840u / O1P_LDS, 2048u / O1P_WG));
-  const u32 groups = std::max(
-      1u, std::min<u32>((n_chunks + O1P_Q - 1) / O1P_Q, (u32)cus * per_cu / O1P_SLICES));
-  hipLaunchKernelGGL(k_histogram_pairs, dim3(groups * O1P_SLICES), dim3(O1P_WG), O1P_LDS, s,
-                     syms, sym_off, n_chunks, pair_hist, first_hist);
-  return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+  return histogram_pairs<false>(ctx, 1, syms, sym_off, n_chunks, pair_hist, first_hist);
 }
 
 rc_status rc_histogram_pairs_periodic(rc_ctx* ctx, uint32_t period, const uint8_t* syms,
                                       const uint64_t* sym_off, uint32_t n_chunks,
                                       uint64_t* pair_hist, uint64_t* first_hist) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (period != 1 && period != 2 && period != 4 && period != 8) return RC_E_ARG;
-  if (n_chunks == 0 || (!pair_hist && !first_hist)) return RC_OK;
-  if (!syms || !sym_off) return RC_E_ARG;
-  DevSet g(dev);
-  rc_svc_yield_all_();
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return RC_E_DEVICE;
-  if (set_allow_lds(reinterpret_cast<const void*>(k_histogram_pairs_periodic)) != hipSuccess)
-    return RC_E_DEVICE;
-  // as rc_histogram_pairs, with 2 P slices side by side
-  const u32 slices = 2u * period;
-  const u32 per_cu = std::max(1u, std::min(163840u / O1P_LDS, 2048u / O1P_WG));
-  const u32 groups =
-      std::max(1u, std::min<u32>((n_chunks + O1P_Q - 1) / O1P_Q, (u32)cus * per_cu / slices));
-  hipLaunchKernelGGL(k_histogram_pairs_periodic, dim3(groups * slices), dim3(O1P_WG), O1P_LDS, s,
-                     period, syms, sym_off, n_chunks, pair_hist, first_hist);
-  return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+  return histogram_pairs<true>(ctx, period, syms, sym_off, n_chunks, pair_hist, first_hist);
 }
 
 rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,
@@ -974,10 +836,9 @@ rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* s
   double* d = nullptr;
   if (hipMallocAsync((void**)&d, icl_bytes, s) != hipSuccess) return RC_E_DEVICE;
   const u32 period = rc_model_order1_period_(o1);  // (> 1: map_dev holds `period` slices)
+  const auto kern = period > 1 ? k_ideal_bits_order1<true> : k_ideal_bits_order1<false>;
   if (hipMemcpyAsync(d, icl, icl_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-      set_allow_lds(period > 1 ? reinterpret_cast<const void*>(k_ideal_bits_o1p)
-                               : reinterpret_cast<const void*>(k_ideal_bits_order1)) !=
-          hipSuccess) {
+      set_allow_lds(reinterpret_cast<const void*>(kern)) != hipSuccess) {
     (void)hipFreeAsync(d, s);
     return RC_E_DEVICE;
   }
@@ -991,12 +852,8 @@ rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* s
   const u32 per_cu = std::max(1u, std::min(8u, 163840u / lds));
   const u32 wg = per_cu == 1 ? 1024u : per_cu < 4 ? 512u : 256u;
   const u32 grid = std::min<u32>((n_chunks + wg / 64 - 1) / (wg / 64), (u32)cus * per_cu);
-  if (period > 1)
-    hipLaunchKernelGGL(k_ideal_bits_o1p, dim3(grid), dim3(wg), lds, s, d, map_dev, period,
-                       first_row, K, syms, sym_off, n_chunks, bits);
-  else
-    hipLaunchKernelGGL(k_ideal_bits_order1, dim3(grid), dim3(wg), lds, s, d, map_dev, first_row,
-                       K, syms, sym_off, n_chunks, bits);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(wg), lds, s, d, map_dev, first_row, K, syms, sym_off,
+                     n_chunks, bits, period);
   const bool ok = hipGetLastError() == hipSuccess;
   // the pinned staging is reused by this thread's next call: wait for the copy
   const bool fr = hipFreeAsync(d, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;

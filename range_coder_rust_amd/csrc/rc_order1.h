@@ -16,19 +16,10 @@
 
 #define O1_MAP_BYTES 1024u  // 256 premultiplied u32 entries
 
-// The set's plan with the decoder's map counted in (enc_*: exactly rc_set_plan's)
-void rc_order1_plan(u32 n_models, u32 total, SetPlan* p);
-
-struct O1Args {
-  SetArgs s;           // the rows and buckets, built for rc_order1_plan's dec_bits
-  const uint8_t* map;  // [256] rows (device): ctx_map, entries from n_symbols on = 0
-  u32 first_row;       // the row of every chunk's first symbol
-};
-
 // Periodic order-1 sets (rc_model_create_order1_set_periodic): the position in a
 // record joins the context, row_i = ctx_map[(i mod P) * n_symbols + sym[i-1]] with P in {1, 2, 4,
-// 8}.  P == 1 is the set above in every respect (same arguments, plan and kernels).  For P > 1
-// both kernels stage P maps of 256 words, slice ph behind slice ph - 1:
+// 8}.  P == 1 is the set above in every respect.  For P > 1 both kernels stage P maps of 256
+// words, slice ph behind slice ph - 1:
 //   encoder: P KiB of its own behind the K rows (the indexed encoder's spare row K holds one map,
 //            not P), so the lanes and the layout are recomputed per (K, total, P);
 //   decoder: P KiB behind the rows in the place of the one.
@@ -37,29 +28,18 @@ static inline bool o1_period_ok(u32 period) {
   return period == 1 || period == 2 || period == 4 || period == 8;
 }
 
-// rc_order1_plan with a period (period 1: exactly rc_order1_plan's; a period that is not one of
-// 1, 2, 4, 8 leaves the plan zeroed)
-void rc_order1_plan_periodic(u32 n_models, u32 total, u32 period, SetPlan* p);
+// The plan of a set of n_models rows coded with `period` maps.  Period 1: the set's plan with the
+// decoder's map counted in (enc_*: exactly rc_set_plan's); a period that is not one of 1, 2, 4, 8
+// leaves the plan zeroed.
+void rc_order1_plan(u32 n_models, u32 total, u32 period, SetPlan* p);
 
-// The periodic kernels' own arguments (O1Args stays as the period-1 kernels take it)
-struct O1PArgs {
-  SetArgs s;           // the rows and buckets, built for rc_order1_plan_periodic's dec_bits
+struct O1Args {
+  SetArgs s;           // the rows and buckets, built for rc_order1_plan's dec_bits
   const uint8_t* map;  // [period][256] rows (device): slice ph = the map of the symbols i with
                        // i mod period == ph, entries from n_symbols on = 0
   u32 first_row;       // the row of every chunk's first symbol
-  u32 period;          // 2, 4 or 8
+  u32 period;          // 1, 2, 4 or 8 (> 1: the launchers take the kernels that stage every slice)
 };
-
-hipError_t rc_order1_encode_launch_periodic(hipStream_t stream, const RcKnobs& k,
-                                            const O1PArgs& a, int div, const SetPlan& p,
-                                            const uint8_t* syms, const u64* sym_off, u32 n_chunks,
-                                            uint8_t* out, const u64* out_off, u64* out_len,
-                                            u32* flags);
-hipError_t rc_order1_decode_launch_periodic(hipStream_t stream, const RcKnobs& k,
-                                            const O1PArgs& a, int div, const SetPlan& p,
-                                            const uint8_t* code, const u64* code_off,
-                                            const u64* code_len, uint8_t* syms_out,
-                                            const u64* sym_off, u32 n_chunks, u32* flags);
 
 hipError_t rc_order1_encode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a, int div,
                                    const SetPlan& p, const uint8_t* syms, const u64* sym_off,

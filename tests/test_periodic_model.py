@@ -241,13 +241,16 @@ def test_periodic_kernels_use_no_scratch_and_128_vgprs():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_check
     res = isa_check.check_library(N.LIB_PATH)
-    names = [k for k in res if "k_encode_o1p" in k or "k_decode_o1p" in k]
+    # (the periodic instantiations: the map policy is part of the mangled name)
+    names = [k for k in res
+             if ("k_encode_order1" in k or "k_decode_order1" in k) and "O1MapP" in k]
     assert len(names) == 6  # encoder: 2 divisions x 2 layouts; decoder: 2 divisions
     for k in names:
         assert res[k][0] == 128 and not res[k][2], (k, res[k])
         assert isa_check.SCRATCH.get(k, 0) == 0, k
-    assert any("k_histogram_pairs_periodic" in k for k in res)
-    assert any("k_ideal_bits_o1p" in k for k in res)
+    # (<true>, mangled ILb1EE: the instantiations with the period)
+    assert any("k_histogram_pairsILb1EE" in k for k in res)
+    assert any("k_ideal_bits_order1ILb1EE" in k for k in res)
 
 
 # ---------------------------------------------------------------- refusals without a device

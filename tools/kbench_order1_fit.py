@@ -16,7 +16,8 @@ composition (`every_run_faster`).  The two results are compared count by count. 
 rc_histogram (batch counts) and one rc_histogram_order1 call (K = 64, map s >> 2).
 
 Ideal bits.  rc_ideal_bits_order1 under sets of K = 1, 8 and 64 rows beside rc_ideal_bits_wide at
-n = 256 on the same symbols widened to 16 bits.  Both calls read their table back and wait for
+n = 256 on the same symbols widened to 16 bits (--period P: the sets are periodic, with P copies
+of the map as their slices, so the periodic kernel sums the same bits).  Both calls read their table back and wait for
 the stream, so the times are of the whole call.  Prints one JSON line per measurement; --out also
 writes them as a JSON list."""
 import argparse
@@ -40,6 +41,8 @@ def main():
     p.add_argument("--steps", type=int, default=3, help="timed runs of the other measurements")
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--k", type=int, nargs="*", default=[1, 8, 64], help="ideal bits: set sizes")
+    p.add_argument("--period", type=int, default=1,
+                   help="ideal bits: the sets' period (> 1: every slice the same map)")
     p.add_argument("--label", default=None, help="copied into every result (build variant)")
     p.add_argument("--out", default=None)
     a = p.parse_args()
@@ -155,13 +158,16 @@ def main():
         del syms16
         for K in a.k:
             rows, cmap = source(K)
-            o1 = rc.Order1ModelSet(rows, None, total, ctx_map=cmap, first_row=0, ctx=ctx)
+            if a.period > 1:
+                cmap = np.tile(cmap, (a.period, 1))
+            o1 = rc.Order1ModelSet(rows, None, total, ctx_map=cmap, first_row=0, ctx=ctx,
+                                   period=a.period)
             fo = lambda: ok(lib.rc_ideal_bits_order1(ctx.handle, o1.handle, _ptr(syms), _ptr(so),
                                                      n, _ptr(bits)))
             for _ in range(a.warmup):
                 fo()
             t = [once(fo) for _ in range(a.steps)]
-            emit(what="rc_ideal_bits_order1", k=K, ms=t, finite=bool(torch.isfinite(bits).all()),
+            emit(what="rc_ideal_bits_order1", k=K, period=a.period, ms=t, finite=bool(torch.isfinite(bits).all()),
                  bits_per_symbol=round(float(bits.sum()) / (n * L), 5))
             o1.close()
     if a.out:

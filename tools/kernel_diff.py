@@ -1,12 +1,16 @@
 """Compare the gfx950 kernels of two builds of the library, kernel by kernel.
 
-    python tools/kernel_diff.py [-v] OLD.so NEW.so
+    python tools/kernel_diff.py [-v] [--rename OLD=NEW]... OLD.so NEW.so
 
 Every kernel of both libraries is disassembled (llvm-objdump -d of each code object, address and
 encoding columns stripped; of a branch only its direction and of a pc-relative address only the
-instruction are kept, since both distances move with any change elsewhere) and the two
-instruction lists are compared.  One line per kernel: identical, added, removed, or differs with the instruction
-counts of both sides and the number that changed.  The VGPR allocation, scratch and static LDS of
+instruction are kept, since both distances move with any change elsewhere; the s_nop padding
+behind a kernel's last s_endpgm is dropped, since it follows the size of the kernel's neighbours)
+and the two instruction lists are compared.  One line per kernel: identical, added, removed, or
+differs with the instruction counts of both sides and the number that changed.  --rename pairs
+kernel OLD of the old library with kernel NEW of the new one (demangled names without return type
+and parameter list, e.g. 'k_decode_o1p<0>=k_decode_order1<0, O1MapP>'), so a renamed kernel is
+compared, not reported as one removed and one added.  The VGPR allocation, scratch and static LDS of
 the kernel descriptors are compared too.  -v prints the differing hunks with a few lines of
 context.  Exit status 0 whatever the result: the tool reports, the engineer judges (DESIGN.md
 §9.9: a refactor may change straight-line setup and finish code of a kernel, never a loop body).
@@ -95,39 +99,93 @@ def demangle(names):
     return dict(zip(names, nice)) if len(nice) == len(names) else {n: n for n in names}
 
 
-def main(argv):
-    verbose = "-v" in argv
-    libs = [a for a in argv if a != "-v"]
-    if len(libs) != 2:
-        print(__doc__)
-        return 0
-    old, new = kernels(libs[0]), kernels(libs[1])
-    names = sorted(set(old) | set(new))
-    nice = demangle(names)
-    count = {"identical": 0, "differs": 0, "added": 0, "removed": 0}
-    for k in names:
-        if k not in old or k not in new:
-            what = "added" if k not in old else "removed"
+
+
+def strip_padding(code):
+    """code without the padding behind its last s_endpgm (s_nop, or zero bytes, which the
+    disassembler prints as "..."): the assembler pads a kernel up to the alignment of the next
+    one, so the padding follows the sizes of the kernel's neighbours"""
+    end = len(code)
+    while end and (code[end - 1].startswith("s_nop") or code[end - 1] == "..."):
+        end -= 1
+    return code[:end] if end and code[end - 1].startswith("s_endpgm") else code
+
+
+def bare(name):
+    """a demangled kernel name without its return type and parameter list: what --rename names"""
+    name = name[5:] if name.startswith("void ") else name
+    depth = 0
+    for i, ch in enumerate(name):
+        depth += (ch == "<") - (ch == ">")
+        if ch == "(" and depth == 0:
+            return name[:i]
+    return name
+
+
+def compare(old, new, renames=(), verbose=False):
+    """old, new: {readable kernel name: ([instruction text], resources)}; renames: (OLD, NEW)
+    pairs of bare names, a kernel OLD of `old` being compared with the kernel NEW of `new`.
+    Returns (report lines, {"identical", "differs", "added", "removed": counts})."""
+    renames = dict(renames)
+    by_bare = {bare(k): k for k in new}
+    pairs, taken = [], set()
+    for k in sorted(old):
+        to = by_bare.get(renames.get(bare(k))) if bare(k) in renames else (k if k in new else None)
+        pairs.append((k, to))
+        taken.add(to)
+    pairs += [(None, k) for k in sorted(new) if k not in taken]
+    lines, count = [], {"identical": 0, "differs": 0, "added": 0, "removed": 0}
+    for ko, kn in sorted(pairs, key=lambda p: p[1] or p[0]):
+        if ko is None or kn is None:
+            what = "added" if ko is None else "removed"
             count[what] += 1
-            print(f"{what:9s} {nice[k]}")
+            lines.append(f"{what:9s} {kn or ko}")
             continue
-        (a, ra), (b, rb) = old[k], new[k]
+        title = kn if ko == kn else f"{kn}  (was {bare(ko)})"
+        (a, ra), (b, rb) = old[ko], new[kn]
+        a, b = strip_padding(a), strip_padding(b)
         res = "" if ra == rb else f"  (VGPRs, scratch, LDS) {ra} -> {rb}"
         if a == b and ra == rb:
             count["identical"] += 1
-            print(f"identical {nice[k]}  [{len(a)} instructions]")
+            lines.append(f"identical {title}  [{len(a)} instructions]")
             continue
         count["differs"] += 1
         sm = difflib.SequenceMatcher(None, a, b, autojunk=False)
         ops = [o for o in sm.get_opcodes() if o[0] != "equal"]
         gone = sum(o[2] - o[1] for o in ops)
         come = sum(o[4] - o[3] for o in ops)
-        print(f"differs   {nice[k]}  [{len(a)} -> {len(b)} instructions, -{gone} +{come} in "
-              f"{len(ops)} hunks]{res}")
+        lines.append(f"differs   {title}  [{len(a)} -> {len(b)} instructions, -{gone} +{come} in "
+                     f"{len(ops)} hunks]{res}")
         if verbose:
-            for line in difflib.unified_diff(a, b, "old", "new", n=3, lineterm=""):
-                print("    " + line)
-    print(", ".join(f"{v} {k}" for k, v in count.items()))
+            lines += ["    " + line for line in difflib.unified_diff(a, b, "old", "new", n=3,
+                                                                      lineterm="")]
+    lines.append(", ".join(f"{v} {k}" for k, v in count.items()))
+    return lines, count
+
+
+def main(argv):
+    verbose, renames, libs = False, [], []
+    args = iter(argv)
+    for a in args:
+        if a == "-v":
+            verbose = True
+        elif a == "--rename" or a.startswith("--rename="):
+            spec = a[9:] if a.startswith("--rename=") else next(args, "")
+            if "=" not in spec:
+                print(__doc__)
+                return 0
+            renames.append(tuple(spec.split("=", 1)))
+        else:
+            libs.append(a)
+    if len(libs) != 2:
+        print(__doc__)
+        return 0
+    both = []
+    for lib in libs:
+        ks = kernels(lib)
+        nice = demangle(sorted(ks))
+        both.append({nice[k]: v for k, v in ks.items()})
+    print("\n".join(compare(both[0], both[1], renames, verbose)[0]))
     return 0
 
 
