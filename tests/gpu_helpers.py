@@ -18,6 +18,50 @@ def cum_of(c):
     return np.concatenate([[0], np.cumsum(c)[:-1]]).astype(np.uint32)
 
 
+def ring_decode_at(call, chunks, off, wide=False):
+    """The layout of the ring tests: the code stream of fixture k at its alignment mod 64 inside
+    64-B slots; the decoded output of every chunk `off` symbols past a 64-B boundary (the
+    fixtures hold one count, a multiple of 64, so contiguous outputs keep it so), which gives the
+    decoders a head of (64 - off) % 64 single symbols (wide, 2-byte symbols: (32 - off) % 32).
+    call(code, code_off, code_len, syms_out, sym_off) -> flags runs the decode.  Returns the
+    whole output buffer (filled with 0xEE bytes before the call, 64 symbols longer than the
+    outputs), sym_off and the flags, as numpy arrays."""
+    codes = [bytes.fromhex(ch["encoded_hex"]) for ch in chunks]
+    counts = {len(ch["symbols"]) for ch in chunks}
+    assert len(counts) == 1 and min(counts) % 64 == 0
+    slot = 64 * ((max(len(c) for c in codes) + 64 + 63) // 64)
+    blob = np.zeros(slot * len(codes) + 64, np.uint8)
+    coff = np.zeros(len(codes), np.int64)
+    for k, (c, ch) in enumerate(zip(codes, chunks)):
+        coff[k] = slot * k + ch["align"]
+        blob[coff[k]:coff[k] + len(c)] = np.frombuffer(c, np.uint8)
+    clen = np.array([len(c) for c in codes], np.int64)
+    sym_off = np.arange(len(codes) + 1, dtype=np.int64) * min(counts) + off
+    if wide:
+        syms = torch.full((int(sym_off[-1]) + 64,), int(np.uint16(0xEEEE).view(np.int16)),
+                          dtype=torch.int16, device="cuda")
+    else:
+        syms = torch.full((int(sym_off[-1]) + 64,), 0xEE, dtype=torch.uint8, device="cuda")
+    flags = call(dev(blob), dev(coff), dev(clen), syms, dev(sym_off))
+    torch.cuda.synchronize()
+    s = syms.cpu().numpy()
+    return (s.view(np.uint16) if wide else s), sym_off, flags.cpu().numpy()
+
+
+def ring_check_exact(s, sym_off, flags, chunks, skip=()):
+    """Every chunk but those in `skip` decoded to its fixture's symbols with no flag, and the
+    sentinels around the outputs are intact."""
+    sent = 0xEEEE if s.dtype == np.uint16 else 0xEE
+    assert (s[:sym_off[0]] == sent).all() and (s[sym_off[-1]:] == sent).all()
+    want = np.array([ch["symbols"] for ch in chunks], s.dtype)
+    got = s[sym_off[0]:sym_off[-1]].reshape(want.shape)
+    keep = np.ones(len(chunks), bool)
+    keep[list(skip)] = False
+    assert (flags[keep] == 0).all(), np.flatnonzero((flags != 0) & keep)[:8]
+    bad = np.flatnonzero((got != want).any(axis=1) & keep)
+    assert not len(bad), bad[:8]
+
+
 def run_encode(model, chunks, caps, misalign=False, seed=0):
     """Encode with chunks at contiguous ragged offsets.  If misalign, prefix the arena with a
     random number of bytes so every chunk (and slot) starts at an arbitrary alignment."""

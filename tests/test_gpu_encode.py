@@ -135,6 +135,25 @@ def test_encoder_on_ring_fixtures(ctx):
         assert bytes(out[out_off[k]:out_off[k] + ol[k]]) == want, k
 
 
+@pytest.mark.parametrize("name", ["pow2", "magic"])
+def test_encoder_on_tight_ring_streams(ctx, name):
+    """The decoders' tight ring streams (tests/golden/ring_tight.json, both of their models)
+    encode to their recorded streams."""
+    with open(os.path.join(HERE, "golden", "ring_tight.json")) as f:
+        fx = json.load(f)
+    md = fx["models"][name]
+    c = np.array(md["c"], np.uint32)
+    m = rc.StaticModel(c, cum_of(c), md["total"])
+    mine = [ch for ch in fx["chunks"] if ch["model"] == name]
+    chunks = [np.array(ch["symbols"], np.uint8) for ch in mine] * 8
+    caps = [rc.slot_capacity(len(ch), 24) for ch in chunks]
+    out, out_off, ol, fl = run_encode(m, chunks, caps, misalign=True, seed=11)
+    for k in range(len(chunks)):
+        want = bytes.fromhex(mine[k % len(mine)]["encoded_hex"])
+        assert fl[k] == 0 and ol[k] == len(want), k
+        assert bytes(out[out_off[k]:out_off[k] + ol[k]]) == want, k
+
+
 @pytest.mark.parametrize("name", ["zipf", "uniform"])
 def test_capacity_end_mid_stream_with_busy_flush_rounds(ctx, name):
     """Slots that end deep inside their streams, on 320 ragged chunks (five waves, so each flush

@@ -6,6 +6,12 @@ steered for (the decoder's 64-B load bursts start on 64-B boundaries).  Every de
 the model (pair buckets at both workgroup sizes, and the bucket decoder) must return the
 fixture's symbols with no flag, also with the output misaligned (a head of single symbols).
 
+The older fixtures leave the ring far from its limit when their heavy spans come (DESIGN.md
+§5.2), so the tight streams (tests/golden/ring_tight.json, made by
+tests/golden/make_ring_tight.py) run through the same variants too: each is steered so that a
+ring check finds just 16 bytes staged before 8 symbols that settle 17, and a decoder whose span
+check staged 16 bytes instead of 24 would decode it wrong.
+
 Run against a scratch `-DRC_RING_GUARD` library (RC_LIB_PATH, tools/ring_guard.py), the same
 assertions show that no symbol read a code byte its ring had not staged: the guard flag would
 make the chunk's flags non-zero."""
@@ -21,7 +27,7 @@ torch = pytest.importorskip("torch")
 
 import range_coder_rust_amd as rc  # noqa: E402
 from oracle import cpu  # noqa: E402
-from gpu_helpers import dev  # noqa: E402
+from gpu_helpers import ring_check_exact, ring_decode_at  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -42,25 +48,7 @@ def ring_fx():
 def _decode_at(m, chunks, head, reps=1):
     """Code stream k at its fixture alignment mod 64 inside 64-B slots; decoded output at
     `head` bytes past a 64-B boundary (plus 64-B aligned chunk strides)."""
-    codes = [bytes.fromhex(ch["encoded_hex"]) for ch in chunks] * reps
-    aligns = [ch["align"] for ch in chunks] * reps
-    counts = [len(ch["symbols"]) for ch in chunks] * reps
-    slot = 64 * ((max(len(c) for c in codes) + 64 + 63) // 64)
-    blob = np.zeros(slot * len(codes) + 64, np.uint8)
-    coff = np.zeros(len(codes), np.int64)
-    for k, (c, a) in enumerate(zip(codes, aligns)):
-        coff[k] = slot * k + a
-        blob[coff[k]:coff[k] + len(c)] = np.frombuffer(c, np.uint8)
-    clen = np.array([len(c) for c in codes], np.int64)
-    # every fixture holds the same count (a multiple of 64): contiguous outputs keep every
-    # chunk's output at `head` past a 64-B boundary
-    assert len(set(counts)) == 1 and counts[0] % 64 == 0
-    sym_off = np.arange(len(codes) + 1, dtype=np.int64) * counts[0] + head
-    syms = torch.full((int(sym_off[-1]) + 64,), 0xEE, dtype=torch.uint8, device="cuda")
-    flags = rc.decode_batch(m, dev(blob), dev(coff), dev(clen), syms, dev(sym_off))
-    torch.cuda.synchronize()
-    s = syms.cpu().numpy()
-    return s, sym_off, flags.cpu().numpy()
+    return ring_decode_at(lambda *a: rc.decode_batch(m, *a), list(chunks) * reps, head)
 
 
 @pytest.mark.parametrize("pair", ["512", "1024", "0"])
@@ -94,3 +82,48 @@ def test_ring_fixtures_full_waves(ctx, ring_fx, knob_ctx):
         f, d = cpu.decode(c, cum, total, bytes.fromhex(ch["encoded_hex"]), len(ch["symbols"]))
         assert f == 0
         assert (s[sym_off[k]:sym_off[k + 1]] == d).all(), k
+
+
+@pytest.fixture(scope="module")
+def tight_fx():
+    with open(os.path.join(HERE, "golden", "ring_tight.json")) as f:
+        return json.load(f)
+
+
+def _tight_model(tight_fx, name, ctx):
+    md = tight_fx["models"][name]
+    m = rc.StaticModel(np.array(md["c"], np.uint32), np.array(md["cum"], np.uint32), md["total"],
+                       ctx=ctx)
+    return m, [ch for ch in tight_fx["chunks"] if ch["model"] == name]
+
+
+# pair buckets at both workgroup sizes, the default dispatch, the direct q-to-symbol table and
+# the buckets (test_gpu_direct_table.py's variants)
+TIGHT_VARIANTS = ["512", "1024", "0", "6", "4"]
+
+
+@pytest.mark.parametrize("pair", TIGHT_VARIANTS)
+@pytest.mark.parametrize("name", ["pow2", "magic"])
+def test_tight_streams_decode(ctx, tight_fx, knob_ctx, name, pair):
+    """Every tight stream of the model at every head some stream of it was steered for (a wide
+    stream's head of h 2-byte symbols is the same schedule as a head of h bytes here), so each
+    at its own head, and at two more (16, 48)."""
+    m, chunks = _tight_model(tight_fx, name, knob_ctx(RC_DEC_PAIR=pair))
+    for head in sorted({ch["head"] for ch in chunks} | {16, 48}):
+        s, sym_off, flags = ring_decode_at(lambda *a: rc.decode_batch(m, *a), chunks,
+                                           (64 - head) % 64)
+        ring_check_exact(s, sym_off, flags, chunks)
+
+
+@pytest.mark.parametrize("pair", ["0", "6"])
+@pytest.mark.parametrize("name", ["pow2", "magic"])
+def test_tight_streams_full_launch(ctx, tight_fx, knob_ctx, name, pair):
+    """The tight streams interleaved and repeated to 1,280 chunks in one launch: more than one
+    workgroup at either size (512 lanes for the buckets, 1,024 for the q-to-symbol table), the
+    last one partly dead, and every wave mixing streams at different points of their schedules."""
+    m, chunks = _tight_model(tight_fx, name, knob_ctx(RC_DEC_PAIR=pair))
+    many = (chunks * (1280 // len(chunks) + 1))[:1280]
+    for head in (0, 5):
+        s, sym_off, flags = ring_decode_at(lambda *a: rc.decode_batch(m, *a), many,
+                                           (64 - head) % 64)
+        ring_check_exact(s, sym_off, flags, many)

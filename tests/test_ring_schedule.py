@@ -1,9 +1,12 @@
 """The static decoder's code-ring schedule on the host (tests/ring_sim.py replays
 k_decode_static's refills and checks, rc_decode.inc): the round-4 schedule never reads a code byte
 before it is staged nor overwrites one before it is read, on the directed ring fixtures
-(tests/golden/ring_fixtures.json, steered to the tightest rings after range_reduction_expansion)
-and on random streams; and the byte bound the schedule rests on (over any s
-symbols of a model with total <= 2^16, no_carry_expansion settles at most 2 s + 2 bytes)."""
+(tests/golden/ring_fixtures.json: a range_reduction_expansion at every span offset, each
+followed by the symbols that settle the most bytes; their rings are not tight, no lowered ring
+need makes one of them under-run: tests/test_ring_tight.py holds the streams that are, and this
+set's measure) and on random streams; and the byte bound the schedule rests on (DESIGN.md §5:
+over any s symbols of a model with total <= 2^16, no_carry_expansion settles at most 2 s + 2
+bytes)."""
 import json
 import os
 
