@@ -544,6 +544,37 @@ rc_status rc_cluster_contexts(const uint64_t* pair_hist_host, const uint64_t* fi
                               uint32_t* first_row_out, uint32_t* n_models_out,
                               double* cost_bits_out);
 
+/* rc_cluster_contexts on the device and over the phases of periodic pair counts jointly, so that
+ * the phases share the rows.  period: 1, 2, 4 or 8.
+ * pair_hist_dev   period x 256 x 256 uint64, as rc_histogram_pairs_periodic writes it (at
+ *                 period 1: rc_histogram_pairs' array); first_hist_dev: 256 uint64.  Device
+ *                 pointers, read stream-ordered and never written.
+ * The items are (phase, context) pairs, item ph * 256 + p being row [ph][p] of the pair counts,
+ * and item period * 256, "start of chunk", with the counts of first_hist_dev: 256 period + 1 in
+ * all.  The rule is rc_cluster_contexts' over these items (one cluster per item with samples in
+ * the slot of its smallest member; the pair with the smallest delta merged while more than
+ * max_models remain; ties to the lexicographically smallest (smallest member of a, smallest
+ * member of b); rows by ascending smallest member; an item without samples gets the lowest row
+ * with the largest total), with the delta taken as cost(a + b) - (cost(a) + cost(b)): symmetric
+ * in a and b, each cost one fixed-order f64 sum of non-negative terms.  At period 1 the items and
+ * the rule are rc_cluster_contexts' own; the two agree unless two deltas of a merge lie within
+ * rounding (about 300 * 2^-52 of cost(a + b)) of each other.
+ * ctx_map_out     host, period x 256: [ph * 256 + p] is the row of item ph * 256 + p; entries
+ *                 with p >= n_symbols are 0.  The first n_symbols entries of every phase are what
+ *                 rc_model_create_order1_set_periodic takes.
+ * first_row_out, n_models_out, cost_bits_out (may be NULL): host, as rc_cluster_contexts.
+ * RC_E_ARG: a period other than 1, 2, 4, 8, a null pointer, max_models outside
+ * 1..RC_MAX_SET_MODELS, n_symbols outside 1..256, counts that sum past 2^63;
+ * RC_E_BAD_SYMBOL: a non-zero count in a row or column >= n_symbols (found first);
+ * RC_E_BAD_MODEL: every count is zero.
+ * The call waits for the stream before it returns (the results go to the host).  Work memory:
+ * 8 (256 period + 1)^2 bytes and about 2 KiB per item, from the stream's memory pool.        */
+rc_status rc_cluster_contexts_dev(rc_ctx* ctx, uint32_t period, const uint64_t* pair_hist_dev,
+                                  const uint64_t* first_hist_dev, uint32_t n_symbols,
+                                  uint32_t max_models, uint8_t* ctx_map_out,
+                                  uint32_t* first_row_out, uint32_t* n_models_out,
+                                  double* cost_bits_out);
+
 /* Batched ideal code length under an order-1 set, straight from the symbols:
  * bits_dev[k] = sum over the symbols i of chunk k of log2(total / c[row_i][sym_i]), f64, with
  * row_0 = first_row and row_i = ctx_map[sym[i-1]] as the order-1 coders pick them (after a

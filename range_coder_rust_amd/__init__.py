@@ -18,8 +18,8 @@ from . import synth  # noqa: F401
 from .model_build import build_model, histogram, ideal_bits, quantize_counts, quantize_counts_wide  # noqa: F401
 from .model_build import build_order1_set, histogram_order1  # noqa: F401
 from .model_build import build_wide_model, histogram_wide, ideal_bits_wide  # noqa: F401
-from .model_build import (cluster_contexts, fit_order1_set, histogram_pairs,  # noqa: F401
-                          histogram_pairs_periodic, ideal_bits_order1)
+from .model_build import (cluster_contexts, cluster_contexts_joint, fit_order1_set,  # noqa: F401
+                          histogram_pairs, histogram_pairs_periodic, ideal_bits_order1)
 from . import container  # noqa: F401
 from .container import (ChecksumError, ContainerError, checksum_batch, compress,  # noqa: F401
                         decompress)

@@ -46,6 +46,7 @@ EXPORTS = (
     "rc_model_create_order1_set_periodic", "rc_histogram_pairs_periodic",
     "rc_checksum_batch", "rc_container2_info_parse", "rc_container2_pack",
     "rc_container2_offsets", "rc_container2_model", "rc_container2_verify",
+    "rc_cluster_contexts_dev",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
@@ -217,9 +218,17 @@ def load():
     # host-only hook of the wide histogram (not in the header; tests/test_gpu_wide_build.py)
     L.rc_histogram_wide_copies_.argtypes = [_U32]
     L.rc_histogram_wide_copies_.restype = _U32
+    # the joint device clustering (a library of an earlier revision has none)
+    cj = ("rc_cluster_contexts_dev",)
+    old4 = not hasattr(L, cj[0])
+    if not old4:
+        L.rc_cluster_contexts_dev.argtypes = [_P, _U32, _P, _P, _U32, _U32, _P,
+                                              ctypes.POINTER(_U32), ctypes.POINTER(_U32),
+                                              ctypes.POINTER(ctypes.c_double)]
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit) \
-                and not (old2 and name in c2) and not (old3 and name in per):
+                and not (old2 and name in c2) and not (old3 and name in per) \
+                and not (old4 and name in cj):
             getattr(L, name).restype = _I
     _lib = L
     return L

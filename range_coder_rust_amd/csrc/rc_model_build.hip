@@ -15,7 +15,9 @@
 //     models (up to 4096 bins; the ideal bits straight from the symbols, without a histogram);
 //   * k_histogram_order1 counts by context class under a given map; k_histogram_pairs counts the
 //     full 256 x 256 pair histogram, rc_cluster_contexts (host) fits a context map to it, and
-//     k_ideal_bits_order1 prices a batch under an order-1 set (rc_order1.h).
+//     k_ideal_bits_order1 prices a batch under an order-1 set (rc_order1.h);
+//   * the k_cj_* kernels are that clustering on the device, jointly over the (phase, context)
+//     items of periodic pair counts (rc_cluster_contexts_dev).
 #include "rc_common.h"
 
 #include <math.h>
@@ -677,6 +679,309 @@ __global__ __launch_bounds__(HWG) void k_ideal_bits_wide(
   }
 }
 
+// ---- rc_cluster_contexts_dev: the greedy clustering of rc_cluster_contexts on the device, over
+// the I = 256 P + 1 items (phase, context) and "start of chunk"  ----
+//
+// Buffers (one hipMallocAsync): V, a private copy of the count rows (I x 256 u64; merges add row
+// b into row a here); per slot cost (f64), tot (u64), live (u32); the delta table D (I x I f64,
+// entries [a][b] with a < b; a dead column holds +inf, a dead row is never read); per row the
+// smallest entry and its column (rmin, rarg: the lexicographically smallest (delta, b)); the
+// merge log.  A stream-ordered chain of kernels, none of which waits for another workgroup:
+//   k_cj_init     one wave per item: the copy, the total (exact, as total >> 32 and its low 32
+//                 bits), the cost, live, and the bad-symbol flag.  The host reads the totals back,
+//                 validates and fixes the number of merges: live items - max_models.
+//   k_cj_pairs    the delta of every live pair: a wave holds row a in registers and walks 64 b.
+//   k_cj_rowmin   one wave per row: rmin, rarg.
+//   k_cj_merge    (one workgroup, per merge) rescans the row of the slot merged last, takes the
+//                 arg-min of (rmin, a) over the live rows, merges b into a (row, total, the merged
+//                 row's cost as cj_cost sums it, live[b] = 0, the log entry).
+//   k_cj_refresh  (one wave per live slot x, per merge) delta(x, a) into D, +inf into column b,
+//                 and row x's minimum: compared with the new entry, or rescanned when its arg-min
+//                 was a or b.  Row a's own minimum is left to the next k_cj_merge, because its
+//                 entries are written by many workgroups.
+// The delta: cost(a + b) - (cost(a) + cost(b)), cost(v) = sum over t = v_s > 0 of
+// t * log2(n / t), n the integer sum.  A lane adds the terms of symbols 4 L .. 4 L + 3 in that
+// order and a butterfly adds the 64 sums, the same in every kernel, without contraction: a delta
+// is a pure function of the two rows and the two costs, symmetric in a and b, and the cost of a
+// merged row equals the cost(a + b) its delta was computed from.  Every term is >= 0.
+#define CJ_NONE 0xFFFFFFFFu
+
+static __device__ __forceinline__ double cj_cost(const u64 t[4], u64 n) {
+#pragma clang fp contract(off)
+  const double dn = (double)n;
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (t[j]) acc += (double)t[j] * log2(dn / (double)t[j]);
+#pragma unroll
+  for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
+  return acc;
+}
+
+// the lexicographically smaller of (d, i) and the same of lane ^ o, over the wave
+static __device__ __forceinline__ void cj_wave_min(double& d, u32& i) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const double d2 = __shfl_xor(d, o);
+    const u32 i2 = (u32)__shfl_xor((int)i, o);
+    if (d2 < d || (d2 == d && i2 < i)) {
+      d = d2;
+      i = i2;
+    }
+  }
+}
+
+static __device__ __forceinline__ void cj_load4(const u64* row, u32 lane, u64 v[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = row[4 * lane + j];
+}
+
+__global__ __launch_bounds__(256) void k_cj_init(
+    const u64* __restrict__ pair, const u64* __restrict__ first, u32 I, u32 n_symbols,
+    u64* __restrict__ V, u64* __restrict__ tot, u64* __restrict__ tot_hi,
+    double* __restrict__ cost, u32* __restrict__ live, u32* __restrict__ hdr) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 item = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= I) return;
+  const bool ctx_item = item + 1 < I;
+  u64 v[4];
+  cj_load4(ctx_item ? pair + (size_t)item * 256 : first, lane, v);
+  bool bad = false;
+  u64 hs = 0, ls = 0;  // sums of the high and the low halves: each below 2^40 over the row
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    bad |= v[j] && (4 * lane + j >= n_symbols || (ctx_item && (item & 255u) >= n_symbols));
+    hs += v[j] >> 32;
+    ls += v[j] & 0xFFFFFFFFull;
+    V[(size_t)item * 256 + 4 * lane + j] = v[j];
+  }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    hs += __shfl_xor((unsigned long long)hs, o);
+    ls += __shfl_xor((unsigned long long)ls, o);
+  }
+  const u64 hi = hs + (ls >> 32);  // total >> 32, exact
+  const u64 t = (hi << 32) | (ls & 0xFFFFFFFFull);
+  const double c = t ? cj_cost(v, t) : 0.0;  // (wave-uniform)
+  const bool anybad = __builtin_amdgcn_ballot_w64(bad) != 0;
+  if (lane == 0) {
+    tot[item] = t;
+    tot_hi[item] = hi;
+    cost[item] = c;
+    live[item] = t != 0;
+    if (anybad) atomicOr(hdr, 1u);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cj_pairs(
+    u32 I, const u64* __restrict__ V, const u64* __restrict__ tot,
+    const double* __restrict__ cost, const u32* __restrict__ live, double* __restrict__ D) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 a = blockIdx.x;
+  const u32 base = blockIdx.y * 256 + (threadIdx.x >> 6) * 64;  // this wave's b: base .. base + 63
+  if (a >= I || base + 63 <= a) return;
+  double mine = INFINITY;
+  if (live[a]) {
+    u64 va[4];
+    cj_load4(V + (size_t)a * 256, lane, va);
+    const double ca = cost[a];
+    const u64 ta = tot[a];
+    for (u32 j = 0; j < 64; ++j) {
+      const u32 b = base + j;
+      if (b <= a || b >= I || !live[b]) continue;  // (wave-uniform)
+      u64 t[4];
+      cj_load4(V + (size_t)b * 256, lane, t);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) t[q] += va[q];
+      const double d = cj_cost(t, ta + tot[b]) - (ca + cost[b]);
+      if (lane == j) mine = d;
+    }
+  }
+  const u32 b = base + lane;
+  if (b > a && b < I) D[(size_t)a * I + b] = mine;
+}
+
+// row x's smallest entry over the columns b > x, (delta, b) lexicographically; column oa reads as
+// da and column ob as +inf whatever D holds (the entries this wave has just written)
+static __device__ __forceinline__ void cj_scan_row(const double* __restrict__ D, u32 I, u32 x,
+                                                   u32 lane, u32 oa, double da, u32 ob, double& d,
+                                                   u32& i) {
+  d = INFINITY;
+  i = CJ_NONE;
+  for (u32 b = x + 1 + lane; b < I; b += 64) {
+    const double v = b == oa ? da : b == ob ? INFINITY : D[(size_t)x * I + b];
+    if (v < d) {
+      d = v;
+      i = b;
+    }
+  }
+  cj_wave_min(d, i);
+}
+
+__global__ __launch_bounds__(256) void k_cj_rowmin(u32 I, const double* __restrict__ D,
+                                                   const u32* __restrict__ live,
+                                                   double* __restrict__ rmin,
+                                                   u32* __restrict__ rarg) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 x = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (x >= I) return;
+  double d = INFINITY;
+  u32 i = CJ_NONE;
+  if (live[x]) cj_scan_row(D, I, x, lane, CJ_NONE, 0.0, CJ_NONE, d, i);
+  if (lane == 0) {
+    rmin[x] = d;
+    rarg[x] = i;
+  }
+}
+
+// hdr[2], hdr[3]: a + 1 and b + 1 of the last merge (0: none yet, or none found)
+__global__ __launch_bounds__(1024) void k_cj_merge(
+    u32 I, u32 m, double* __restrict__ D, u64* __restrict__ V, u64* __restrict__ tot,
+    double* __restrict__ cost, u32* __restrict__ live, double* __restrict__ rmin,
+    u32* __restrict__ rarg, u32* __restrict__ hdr, u32* __restrict__ log) {
+  __shared__ double s_d[16];
+  __shared__ u32 s_i[16];
+  __shared__ double s_rd;
+  __shared__ u32 s_ri;
+  const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the workgroup's lexicographically smallest (d, i), into s_rd, s_ri
+  auto reduce = [&](double d, u32 i) {
+    cj_wave_min(d, i);
+    __syncthreads();
+    if (lane == 0) {
+      s_d[wave] = d;
+      s_i[wave] = i;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      d = lane < 16 ? s_d[lane] : INFINITY;
+      i = lane < 16 ? s_i[lane] : CJ_NONE;
+      cj_wave_min(d, i);
+      if (lane == 0) {
+        s_rd = d;
+        s_ri = i;
+      }
+    }
+    __syncthreads();
+  };
+  const u32 prev = hdr[2] - 1u;  // the slot merged last: its row of D is new
+  double pd = INFINITY;
+  u32 pb = CJ_NONE;
+  if (prev < I) {
+    double d = INFINITY;
+    u32 i = CJ_NONE;
+    for (u32 b = prev + 1 + tid; b < I; b += 1024) {
+      const double v = D[(size_t)prev * I + b];
+      if (v < d) {
+        d = v;
+        i = b;
+      }
+    }
+    reduce(d, i);
+    pd = s_rd;
+    pb = s_ri;
+    if (tid == 0) {
+      rmin[prev] = pd;
+      rarg[prev] = pb;
+    }
+  }
+  double d = INFINITY;
+  u32 i = CJ_NONE;
+  for (u32 r = tid; r < I; r += 1024) {
+    if (!live[r]) continue;
+    const double v = r == prev ? pd : rmin[r];
+    if (v < d) {
+      d = v;
+      i = r;
+    }
+  }
+  reduce(d, i);
+  const u32 a = s_ri;
+  const u32 b = a < I ? (a == prev ? pb : rarg[a]) : CJ_NONE;
+  if (wave != 0) return;
+  if (a >= I || b >= I || b <= a) {  // no live pair: nothing is merged (the host sees the log)
+    if (lane == 0) {
+      log[2 * m] = CJ_NONE;
+      log[2 * m + 1] = CJ_NONE;
+      hdr[2] = 0;
+      hdr[3] = 0;
+    }
+    return;
+  }
+  u64 t[4], vb[4];
+  cj_load4(V + (size_t)a * 256, lane, t);
+  cj_load4(V + (size_t)b * 256, lane, vb);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    t[q] += vb[q];
+    V[(size_t)a * 256 + 4 * lane + q] = t[q];
+  }
+  const u64 n = tot[a] + tot[b];
+  const double c = cj_cost(t, n);
+  if (lane == 0) {
+    tot[a] = n;
+    cost[a] = c;
+    live[b] = 0;
+    log[2 * m] = a;
+    log[2 * m + 1] = b;
+    hdr[2] = a + 1;
+    hdr[3] = b + 1;
+    D[(size_t)a * I + b] = INFINITY;  // column b is dead in row a too (no wave refreshes x = b)
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cj_refresh(
+    u32 I, const u64* __restrict__ V, const u64* __restrict__ tot,
+    const double* __restrict__ cost, const u32* __restrict__ live, double* __restrict__ D,
+    double* __restrict__ rmin, u32* __restrict__ rarg, const u32* __restrict__ hdr) {
+  const u32 lane = threadIdx.x & 63;
+  const u32 x = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const u32 a = hdr[2] - 1u, b = hdr[3] - 1u;
+  if (a >= I || b >= I || x >= I || x == a || !live[x]) return;  // (b is no longer live)
+  u64 t[4], vx[4];
+  cj_load4(V + (size_t)a * 256, lane, t);
+  cj_load4(V + (size_t)x * 256, lane, vx);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) t[q] += vx[q];
+  const double d = cj_cost(t, tot[a] + tot[x]) - (cost[a] + cost[x]);
+  const u32 r = rarg[x];
+  if (x > a) {
+    if (lane == 0) D[(size_t)a * I + x] = d;
+    if (x < b) {
+      if (lane == 0) D[(size_t)x * I + b] = INFINITY;
+      if (r == b) {
+        double nd;
+        u32 ni;
+        cj_scan_row(D, I, x, lane, CJ_NONE, 0.0, b, nd, ni);
+        if (lane == 0) {
+          rmin[x] = nd;
+          rarg[x] = ni;
+        }
+      }
+    }
+    return;
+  }
+  if (lane == 0) {
+    D[(size_t)x * I + a] = d;
+    D[(size_t)x * I + b] = INFINITY;
+  }
+  if (r == a || r == b) {
+    double nd;
+    u32 ni;
+    cj_scan_row(D, I, x, lane, a, d, b, nd, ni);
+    if (lane == 0) {
+      rmin[x] = nd;
+      rarg[x] = ni;
+    }
+  } else if (lane == 0) {
+    const double old = rmin[x];
+    if (d < old || (d == old && a < r)) {
+      rmin[x] = d;
+      rarg[x] = a;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------
@@ -1134,6 +1439,119 @@ rc_status rc_cluster_contexts(const uint64_t* pair_hist, const uint64_t* first_h
   *n_models_out = (u32)live.size();
   if (cost_bits_out) *cost_bits_out = bits;
   return RC_OK;
+}
+
+// rc_cluster_contexts_dev: rc_cluster_contexts' rule over the 256 P + 1 items of periodic pair
+// counts, on the device where they lie (the k_cj_* kernels above).  Two waits: after k_cj_init
+// (the totals: validation, and the number of merges, which the host fixes before it enqueues the
+// loop) and at the end (the log and the costs).  The host replays the log into slots and rows.
+rc_status rc_cluster_contexts_dev(rc_ctx* ctx, uint32_t period, const uint64_t* pair_hist,
+                                  const uint64_t* first_hist, uint32_t n_symbols,
+                                  uint32_t max_models, uint8_t* ctx_map_out,
+                                  uint32_t* first_row_out, uint32_t* n_models_out,
+                                  double* cost_bits_out) {
+  hipStream_t s;
+  int dev;
+  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK) return RC_E_ARG;
+  if (period != 1 && period != 2 && period != 4 && period != 8) return RC_E_ARG;
+  if (!pair_hist || !first_hist || !ctx_map_out || !first_row_out || !n_models_out ||
+      max_models < 1 || max_models > RC_MAX_SET_MODELS || n_symbols < 1 || n_symbols > 256)
+    return RC_E_ARG;
+  DevSet g(dev);
+  rc_svc_yield_all_();
+  const u32 I = 256u * period + 1u;
+  // one allocation: D, V, cost, rmin, tot, tot_hi (8-byte entries), then live, rarg, log, hdr
+  const size_t n8 = (size_t)I * I + (size_t)I * 256 + 5 * (size_t)I;
+  const size_t n4 = 4 * (size_t)I + 4;
+  // pinned staging: tot, tot_hi, cost (8-byte entries), then hdr and the log
+  char* pin = (char*)rc_pinned_scratch_(3 * (size_t)I * 8 + 16 + 2 * (size_t)I * 4);
+  if (!pin) return RC_E_DEVICE;
+  char* buf = nullptr;
+  if (hipMallocAsync((void**)&buf, n8 * 8 + n4 * 4, s) != hipSuccess) return RC_E_DEVICE;
+  double* D = (double*)buf;
+  u64* V = (u64*)(D + (size_t)I * I);
+  double* cost = (double*)(V + (size_t)I * 256);
+  double* rmin = cost + I;
+  u64* tot = (u64*)(rmin + I);
+  u64* tot_hi = tot + I;
+  u32* live = (u32*)(tot_hi + I);
+  u32* rarg = live + I;
+  u32* log = rarg + I;
+  u32* hdr = log + 2 * (size_t)I;
+  u64* h_tot = (u64*)pin;
+  u64* h_hi = h_tot + I;
+  double* h_cost = (double*)(h_hi + I);
+  u32* h_hdr = (u32*)(h_cost + I);
+  u32* h_log = h_hdr + 4;
+  auto done = [&](rc_status st) {
+    const bool fr = hipFreeAsync(buf, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    return st == RC_OK && !fr ? RC_E_DEVICE : st;
+  };
+  const u32 waves4 = (I + 3) / 4;  // workgroups of four waves, one wave per item
+  if (hipMemsetAsync(hdr, 0, 16, s) != hipSuccess) return done(RC_E_DEVICE);
+  hipLaunchKernelGGL(k_cj_init, dim3(waves4), dim3(256), 0, s, pair_hist, first_hist, I, n_symbols,
+                     V, tot, tot_hi, cost, live, hdr);
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(h_tot, tot, 2 * (size_t)I * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(h_hdr, hdr, 16, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return done(RC_E_DEVICE);
+  if (h_hdr[0] & 1u) return done(RC_E_BAD_SYMBOL);
+  unsigned __int128 all = 0;
+  std::vector<u64> htot(I);
+  std::vector<u32> slot(I), live_h;  // slot: an item's cluster (I: not clustered)
+  for (u32 a = 0; a < I; ++a) {
+    all += ((unsigned __int128)h_hi[a] << 32) | (h_tot[a] & 0xFFFFFFFFull);
+    htot[a] = h_tot[a];
+    slot[a] = h_tot[a] ? a : I;
+    if (h_tot[a]) live_h.push_back(a);
+  }
+  if (all >> 63) return done(RC_E_ARG);
+  if (all == 0) return done(RC_E_BAD_MODEL);
+  const u32 merges = live_h.size() > max_models ? (u32)live_h.size() - max_models : 0u;
+  if (merges) {
+    hipLaunchKernelGGL(k_cj_pairs, dim3(I, (I + 255) / 256), dim3(256), 0, s, I, V, tot, cost,
+                       live, D);
+    hipLaunchKernelGGL(k_cj_rowmin, dim3(waves4), dim3(256), 0, s, I, D, live, rmin, rarg);
+    for (u32 m = 0; m < merges; ++m) {
+      hipLaunchKernelGGL(k_cj_merge, dim3(1), dim3(1024), 0, s, I, m, D, V, tot, cost, live, rmin,
+                         rarg, hdr, log);
+      if (m + 1 < merges)
+        hipLaunchKernelGGL(k_cj_refresh, dim3(waves4), dim3(256), 0, s, I, V, tot, cost, live, D,
+                           rmin, rarg, hdr);
+    }
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(h_log, log, 2 * (size_t)merges * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+      return done(RC_E_DEVICE);
+  }
+  if (hipMemcpyAsync(h_cost, cost, (size_t)I * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return done(RC_E_DEVICE);
+  // replay the log: b's members join a's slot
+  for (u32 m = 0; m < merges; ++m) {
+    const u32 a = h_log[2 * m], b = h_log[2 * m + 1];
+    if (a >= b || b >= I || slot[a] != a || slot[b] != b) return done(RC_E_DEVICE);
+    htot[a] += htot[b];
+    for (u32 x = 0; x < I; ++x)
+      if (slot[x] == b) slot[x] = a;
+    live_h.erase(std::find(live_h.begin(), live_h.end(), b));
+  }
+  // rows by ascending smallest member (live_h is ascending); the largest row, lowest on ties
+  std::vector<u32> row(I + 1, 0);
+  u32 big = 0;
+  double bits = 0.0;
+  for (size_t i = 0; i < live_h.size(); ++i) {
+    row[live_h[i]] = (u32)i;
+    if (htot[live_h[i]] > htot[live_h[big]]) big = (u32)i;
+    bits += h_cost[live_h[i]];
+  }
+  row[I] = big;  // items without samples
+  for (u32 x = 0; x + 1 < I; ++x)
+    ctx_map_out[x] = (x & 255u) < n_symbols ? (uint8_t)row[slot[x]] : 0;
+  *first_row_out = row[slot[I - 1]];
+  *n_models_out = (u32)live_h.size();
+  if (cost_bits_out) *cost_bits_out = bits;
+  return done(RC_OK);
 }
 
 rc_status rc_ideal_bits(rc_ctx* ctx, const uint32_t* c_host, uint32_t n_symbols,

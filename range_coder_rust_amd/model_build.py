@@ -18,6 +18,8 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
                                   histogram of the chunks' first symbols (HIP)
   cluster_contexts(pair, first, K)           rc_cluster_contexts: those counts -> a context map
                                   of at most K classes and a first_row (host)
+  cluster_contexts_joint(pair, first, K)     rc_cluster_contexts_dev: the same on the device, over
+                                  the (phase, context) items of periodic pair counts (HIP)
   fit_order1_set(syms, sym_off, K)           pairs -> map -> class counts -> Order1ModelSet
   ideal_bits_order1(model, syms, sym_off)    rc_ideal_bits_order1: per-chunk ideal bits of an
                                   order-1 set, straight from the symbols (HIP)
@@ -261,8 +263,43 @@ def cluster_contexts(pair_hist, first_hist, n_models=64, n_symbols=256):
     return cm[:int(n_symbols)], int(first_row.value), int(k.value), float(cost.value)
 
 
+def cluster_contexts_joint(pair_hist, first_hist, n_models=64, n_symbols=256, ctx=None):
+    """rc_cluster_contexts_dev: cluster_contexts on the device, jointly over the (phase, context)
+    items of periodic pair counts, so that the phases share the n_models rows.
+
+    pair_hist: a device tensor int64/uint64 [P, 256, 256] (P = 1, 2, 4 or 8) as
+    histogram_pairs_periodic gives it, or [256, 256] for P = 1; first_hist: [256].  Neither is
+    written.  Returns (ctx_map, first_row, n_models, cost_bits) as cluster_contexts does, with
+    ctx_map uint8[P, n_symbols] ([n_symbols] for a [256, 256] input).  The call waits for the
+    stream."""
+    torch = _torch()
+    _check_dev(pair_hist, "pair_hist", (torch.int64, torch.uint64))
+    _check_dev(first_hist, "first_hist", (torch.int64, torch.uint64))
+    flat = pair_hist.dim() == 2
+    shape = tuple(pair_hist.shape)
+    period = 1 if flat else (shape[0] if len(shape) == 3 else 0)
+    if period not in (1, 2, 4, 8) or shape[-2:] != (256, 256) or tuple(first_hist.shape) != (256,):
+        raise ValueError("pair_hist must be [P, 256, 256] (P = 1, 2, 4 or 8) or [256, 256], "
+                         "and first_hist [256]")
+    ctx = ctx or default_context(pair_hist.device.index)
+    cm = np.zeros((period, 256), np.uint8)
+    first_row, k, cost = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_double()
+    ctx.bind_stream()
+    rc = ctx._lib.rc_cluster_contexts_dev(ctx.handle, period, _ptr(pair_hist), _ptr(first_hist),
+                                          int(n_symbols), int(n_models),
+                                          ctypes.c_void_p(cm.ctypes.data), ctypes.byref(first_row),
+                                          ctypes.byref(k), ctypes.byref(cost))
+    if rc == N.RC_E_BAD_SYMBOL:
+        raise ValueError(f"symbols >= {int(n_symbols)} present")
+    if rc == N.RC_E_BAD_MODEL:
+        raise ValueError("no context map for empty counts")
+    N.check(rc, "rc_cluster_contexts_dev")
+    cm = cm[:, :int(n_symbols)]
+    return (cm[0] if flat else cm), int(first_row.value), int(k.value), float(cost.value)
+
+
 def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=256, ctx=None,
-                   period=1):
+                   period=1, joint=False):
     """An Order1ModelSet fitted to the batch: pair counts on the GPU (histogram_pairs), a context
     map of at most n_models classes from them (cluster_contexts), the classes' counts on the GPU
     (histogram_order1 with the map found) and their quantised rows.  The set's ctx_map and
@@ -274,14 +311,33 @@ def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=2
     ValueError if n_models < period), phase ph's rows numbered after those of the phases before
     it, the classes' counts summed on the host from the pair counts (no second pass over the
     symbols) and the rows quantised.  That is `period` runs of the host clustering, about 0.17 s
-    each, and the phases cannot share a row: every phase gets the same number
-    of classes whether it needs them or not."""
+    each, and without `joint` the phases cannot share a row: every phase gets
+    the same number of classes whether it needs them or not.
+
+    joint=True clusters on the device instead (cluster_contexts_joint), on the
+    pair counts where they lie: all the (phase, context) items at once, so the n_models rows are
+    shared by the phases as the data asks, and n_models < period is allowed.  The classes'
+    counts are summed on the host from the pair counts as above.  At period 1 only the
+    clustering moves to the device; the rest is as without `joint`."""
     period = int(period)
     if period not in (1, 2, 4, 8):
         raise ValueError("period must be 1, 2, 4 or 8")
-    if int(n_models) < period:
+    if int(n_models) < period and not joint:
         raise ValueError(f"n_models = {n_models} leaves a phase of period {period} no row")
     ctx = ctx or default_context(syms.device.index)
+    if joint and period != 1:
+        pair_t, first_t = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx)
+        cm, first_row, k, _ = cluster_contexts_joint(pair_t, first_t, n_models, n_symbols, ctx=ctx)
+        maps = np.zeros((period, 256), np.uint8)
+        maps[:, :cm.shape[1]] = cm
+        counts = _class_counts(pair_t.cpu().numpy(), first_t.cpu().numpy(), maps, first_row, k)
+        return Order1ModelSet.from_counts(counts[:, :n_symbols], maps[:, :n_symbols], first_row,
+                                          target_total, ctx=ctx, period=period)
+    if joint:
+        pair, first = histogram_pairs(syms, sym_off, ctx=ctx)
+        cm, first_row, k, _ = cluster_contexts_joint(pair, first, n_models, n_symbols, ctx=ctx)
+        return build_order1_set(syms, sym_off, cm, first_row, target_total, n_symbols, n_models=k,
+                                ctx=ctx)
     if period != 1:
         pair_t, first_t = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx)
         pair, first = pair_t.cpu().numpy(), first_t.cpu().numpy()
