@@ -268,6 +268,31 @@ rc_status rc_model_create_order1_set_periodic(rc_ctx* ctx, uint32_t n_models, ui
                                               const uint32_t* cum_freq_host, uint32_t total_freq,
                                               uint32_t period, const uint8_t* ctx_map_host,
                                               uint32_t first_row, rc_model** out);
+/* An order-1 set with a lag: the context is the symbol `lag` positions back.  In a tensor of 2-,
+ * 4- or 8-byte records the byte before a symbol is another field of the same number; the byte
+ * that tells most about it is the same byte of the record before, sym[i-P].  With lag D and
+ * period P, each in {1, 2, 4, 8} and independent of each other:
+ *   the row of symbol i < D of every chunk is first_row;
+ *   the row of symbol i >= D is ctx_map[(i mod P) * n_symbols + sym[i-D]], i counted from the
+ *   chunk's first symbol.
+ * Everything else is rc_model_create_order1_set_periodic's: the same rules for the tables and
+ * the map (period x n_symbols bytes, entries from n_symbols on name row 0 when staged), the same
+ * coding of symbol i as encoder.encode(&models[row_i], sym[i]) / decoder.decode(&models[row_i]),
+ * bit-exactly, the same flags, slots and over-read rule, and the first error of a chunk wins.
+ * A lag or a period outside {1, 2, 4, 8} is RC_E_ARG; a map entry or first_row >= n_models is
+ * RC_E_BAD_MODEL.
+ * The result is an order-1 set: rc_encode_batch_order1, rc_decode_batch_order1 and
+ * rc_ideal_bits_order1 take it as they are and dispatch on its lag.  With lag 1 the call is
+ * rc_model_create_order1_set_periodic itself (same kernels, same bytes).  A lagged set needs no
+ * more local memory than the periodic set of its (n_models, total_freq, period).  A set with
+ * lag > 1 is refused (RC_E_ARG) by every other entry point that takes a model, rc_container2_pack
+ * included: RCB2 has no field for a lag.                                                     */
+rc_status rc_model_create_order1_set_lagged(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                            const uint32_t* c_freq_host,
+                                            const uint32_t* cum_freq_host, uint32_t total_freq,
+                                            uint32_t period, uint32_t lag,
+                                            const uint8_t* ctx_map_host, uint32_t first_row,
+                                            rc_model** out);
 /* rc_encode_batch with the row chosen by the chunk's previous symbol.
  * flags_dev     RC_F_BAD_SYMBOL for a symbol >= n_symbols, RC_F_ZERO_FREQ against the row the
  *               context chose, RC_F_CAPACITY with the exact length in out_len, RC_F_TOO_LONG; the
@@ -521,6 +546,23 @@ rc_status rc_histogram_pairs_periodic(rc_ctx* ctx, uint32_t period, const uint8_
                                       const uint64_t* sym_off_dev, uint32_t n_chunks,
                                       uint64_t* pair_hist_dev, uint64_t* first_hist_dev);
 
+/* rc_histogram_pairs_periodic with the pairs taken at a distance: what the maps of a lagged
+ * order-1 set are fitted from.  period and lag: each 1, 2, 4 or 8 (else RC_E_ARG).
+ * pair_hist_dev   NULL or period x 256 x 256 uint64: [ph][p][s] is increased by the number of
+ *                 positions i >= lag of a chunk with i mod period = ph, sym[i-lag] = p and
+ *                 sym[i] = s (i counted from the chunk's first symbol)
+ * first_hist_dev  NULL or 256 uint64: [s] is increased by the number of positions i < lag of a
+ *                 chunk with sym[i] = s: a chunk of n symbols adds min(lag, n) counts, the symbols
+ *                 that a lagged set codes with first_row
+ * So sum(pair) + sum(first) is the number of symbols.  Chunk boundaries reset the context; counts
+ * are ADDED into the arrays and are exact for any data; with both results NULL the call does
+ * nothing (RC_OK).  With lag 1 the call is rc_histogram_pairs_periodic.  Device pointers;
+ * stream-ordered.                                                                            */
+rc_status rc_histogram_pairs_lagged(rc_ctx* ctx, uint32_t period, uint32_t lag,
+                                    const uint8_t* syms_dev, const uint64_t* sym_off_dev,
+                                    uint32_t n_chunks, uint64_t* pair_hist_dev,
+                                    uint64_t* first_hist_dev);
+
 /* Pair counts -> a context map of at most max_models classes and a first_row (host only, no
  * device needed; deterministic): greedy agglomerative clustering under the empirical-entropy
  * cost(v) = sum over v_s > 0 of v_s * log2(sum(v) / v_s), in f64.
@@ -579,7 +621,8 @@ rc_status rc_cluster_contexts_dev(rc_ctx* ctx, uint32_t period, const uint64_t* 
  * bits_dev[k] = sum over the symbols i of chunk k of log2(total / c[row_i][sym_i]), f64, with
  * row_0 = first_row and row_i = ctx_map[sym[i-1]] as the order-1 coders pick them (after a
  * symbol >= n_symbols the next row is row 0, as they stage the map); for a periodic set
- * row_i = ctx_map[(i mod P) * n_symbols + sym[i-1]], with the same sums.  A term with c == 0 or a
+ * row_i = ctx_map[(i mod P) * n_symbols + sym[i-1]], for a lagged set first_row for i < D and
+ * ctx_map[(i mod P) * n_symbols + sym[i-D]] from there on, with the same sums.  A term with c == 0 or a
  * symbol >= n_symbols makes its chunk +inf; an empty chunk is 0.0; nothing is NaN.
  * `o1` must be an order-1 set of this context's device (RC_E_ARG for any other kind of model).
  * Stream-ordered; the call waits for the stream (it reads the set's rows back to price them on

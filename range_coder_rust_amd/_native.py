@@ -47,6 +47,7 @@ EXPORTS = (
     "rc_checksum_batch", "rc_container2_info_parse", "rc_container2_pack",
     "rc_container2_offsets", "rc_container2_model", "rc_container2_verify",
     "rc_cluster_contexts_dev",
+    "rc_model_create_order1_set_lagged", "rc_histogram_pairs_lagged",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
@@ -225,10 +226,21 @@ def load():
         L.rc_cluster_contexts_dev.argtypes = [_P, _U32, _P, _P, _U32, _U32, _P,
                                               ctypes.POINTER(_U32), ctypes.POINTER(_U32),
                                               ctypes.POINTER(ctypes.c_double)]
+    # lagged order-1 sets (a library of an earlier revision has none of these)
+    lag = ("rc_model_create_order1_set_lagged", "rc_histogram_pairs_lagged")
+    old5 = not hasattr(L, lag[0])
+    if not old5:
+        L.rc_model_create_order1_set_lagged.argtypes = [_P, _U32, _U32, _P, _P, _U32, _U32, _U32,
+                                                        _P, _U32, ctypes.POINTER(_P)]
+        L.rc_histogram_pairs_lagged.argtypes = [_P, _U32, _U32, _P, _P, _U32, _P, _P]
+        L.rc_model_order1_check_lagged_.argtypes = [_U32, _U32, _P, _P, _U32, _U32, _U32, _P, _U32]
+        L.rc_model_order1_check_lagged_.restype = _I
+        L.rc_model_order1_plan_lagged_.argtypes = [_U32, _U32, _U32, _U32, _P]
+        L.rc_model_order1_plan_lagged_.restype = _I
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit) \
                 and not (old2 and name in c2) and not (old3 and name in per) \
-                and not (old4 and name in cj):
+                and not (old4 and name in cj) and not (old5 and name in lag):
             getattr(L, name).restype = _I
     _lib = L
     return L

@@ -492,10 +492,16 @@ class Order1ModelSet:
     the context.  ctx_map is then [period, n_symbols] and symbol i > 0 is coded with row
     ctx_map[i % period, sym[i-1]], i counted from the chunk's start (for period 1 a flat map is
     still accepted).  The order-1 batch calls and ideal_bits_order1 take such a set as they are;
-    a container cannot frame a period, so pack() and compress() raise for period > 1."""
+    a container cannot frame a period, so pack() and compress() raise for period > 1.
+
+    lag (1, 2, 4 or 8; rc_model_create_order1_set_lagged): the context is the symbol `lag`
+    positions back, the same byte of the record before when lag is the record's size.  Symbol
+    i >= lag is coded with row ctx_map[i % period, sym[i-lag]] and every symbol i < lag with
+    first_row.  Period and lag are independent; lag 1 is the set without one.  A container
+    cannot frame a lag either."""
 
     def __init__(self, c_rows, cum_rows=None, total_freq=None, ctx_map=None, first_row=0,
-                 ctx=None, period=1):
+                 ctx=None, period=1, lag=1):
         c = np.ascontiguousarray(c_rows, dtype=np.uint32)
         if c.ndim != 2:
             raise ValueError("c_rows must be K x n_symbols")
@@ -516,6 +522,9 @@ class Order1ModelSet:
         period = int(period)
         if period not in (1, 2, 4, 8):
             raise ValueError("period must be 1, 2, 4 or 8")
+        lag = int(lag)
+        if lag not in (1, 2, 4, 8):
+            raise ValueError("lag must be 1, 2, 4 or 8")
         if cm.ndim == 2 and cm.shape[0] == period and cm.shape[1] >= self.n_symbols:
             cm = cm[:, :self.n_symbols].astype(np.int64)
             if period == 1:
@@ -534,14 +543,20 @@ class Order1ModelSet:
         self.ctx_map = np.ascontiguousarray(cm, dtype=np.uint8)
         self.first_row = first_row
         self.period = period
+        self.lag = lag
         self._ctx = ctx
         self._handle = None
         tables = (self.n_models, self.n_symbols, ctypes.c_void_p(c.ctypes.data),
                   ctypes.c_void_p(cum.ctypes.data), ctypes.c_uint32(self.total & 0xFFFFFFFF))
         where = (ctypes.c_void_p(self.ctx_map.ctypes.data), ctypes.c_uint32(self.first_row))
-        # (period 1 goes through the calls it always did)
-        rc = (N.load().rc_model_order1_check_(*tables, *where) if period == 1 else
-              N.load().rc_model_order1_check_periodic_(*tables, ctypes.c_uint32(period), *where))
+        # (period 1 and lag 1 go through the calls they always did)
+        if lag != 1:
+            rc = N.load().rc_model_order1_check_lagged_(*tables, ctypes.c_uint32(period),
+                                                        ctypes.c_uint32(lag), *where)
+        else:
+            rc = (N.load().rc_model_order1_check_(*tables, *where) if period == 1 else
+                  N.load().rc_model_order1_check_periodic_(*tables, ctypes.c_uint32(period),
+                                                           *where))
         if rc != N.RC_OK or self.total > 0xFFFFFFFF:
             raise ValueError(
                 f"order-1 set rejected: need 1..{N.MAX_SET_MODELS} rows of 1..256 symbols, one "
@@ -550,14 +565,14 @@ class Order1ModelSet:
 
     @classmethod
     def from_counts(cls, count_rows, ctx_map, first_row=0, target_total=65536, ctx=None,
-                    period=1):
+                    period=1, lag=1):
         """One row per context class from its histogram (rc_histogram_order1's rows), each scaled
         to target_total with every symbol kept encodable (rc_quantize_counts with
         RC_Q_ALL_SYMBOLS)."""
         from .model_build import quantize_counts
         rows = [quantize_counts(r, target_total, all_symbols=True) for r in count_rows]
         return cls([r[0] for r in rows], [r[1] for r in rows], int(target_total),
-                   ctx_map=ctx_map, first_row=first_row, ctx=ctx, period=period)
+                   ctx_map=ctx_map, first_row=first_row, ctx=ctx, period=period, lag=lag)
 
     def derive_indexes(self, syms):
         """The index stream the indexed calls would take for one chunk of symbols (host)."""
@@ -566,8 +581,9 @@ class Order1ModelSet:
         if len(s):
             m = np.zeros((self.period, 256), np.uint8)
             m[:, :self.n_symbols] = self.ctx_map.reshape(self.period, self.n_symbols)
-            idx[0] = self.first_row
-            idx[1:] = m[np.arange(1, len(s)) % self.period, s[:-1]]
+            D = self.lag
+            idx[:D] = self.first_row
+            idx[D:] = m[np.arange(D, len(s)) % self.period, s[:-D]]
         return idx
 
     ctx = StaticModelSet.ctx
@@ -581,7 +597,11 @@ class Order1ModelSet:
                       ctypes.c_uint32(self.total))
             where = (ctypes.c_void_p(self.ctx_map.ctypes.data), ctypes.c_uint32(self.first_row),
                      ctypes.byref(h))
-            if self.period == 1:
+            if self.lag != 1:
+                N.check(self.ctx._lib.rc_model_create_order1_set_lagged(
+                    *tables, ctypes.c_uint32(self.period), ctypes.c_uint32(self.lag), *where),
+                    "rc_model_create_order1_set_lagged")
+            elif self.period == 1:
                 N.check(self.ctx._lib.rc_model_create_order1_set(*tables, *where),
                         "rc_model_create_order1_set")
             else:

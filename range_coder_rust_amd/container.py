@@ -94,6 +94,10 @@ def _refuse_period(model):
     if isinstance(model, Order1ModelSet) and model.period > 1:
         raise ValueError(f"a container cannot frame an Order1ModelSet with period "
                          f"{model.period}: keep the set beside the code, or use period 1")
+    # (RCB2 has no field for a lag either: rc_container2_pack returns RC_E_ARG for lag > 1)
+    if isinstance(model, Order1ModelSet) and model.lag > 1:
+        raise ValueError(f"a container cannot frame an Order1ModelSet with lag {model.lag}: "
+                         f"keep the set beside the code, or use lag 1")
 
 
 def pack(model, slots, slot_off, code_len, sym_off, sums=None, rcb2=False):
@@ -177,7 +181,7 @@ def _model_of2(container, inf, ctx):
         m = Order1ModelSet.__new__(Order1ModelSet)
         m.c, m.cum, m.n_models = c, cum, k
         m.ctx_map = tab[4 * k * n:4 * k * n + n].copy()
-        m.first_row, m.period = inf.first_row, 1
+        m.first_row, m.period, m.lag = inf.first_row, 1, 1
     else:
         cls = StaticModel if inf.kind == 0 else WideStaticModel
         m = cls.__new__(cls)

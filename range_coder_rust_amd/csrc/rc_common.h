@@ -298,3 +298,5 @@ bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** 
                            u32* first_row, u32* n_models, u32* n_symbols, int* device);
 // the period of an order-1 set (1, 2, 4 or 8); 0 for any other kind of model
 u32 rc_model_order1_period_(const rc_model* m);
+// the lag of an order-1 set (1, 2, 4 or 8); 0 for any other kind of model
+u32 rc_model_order1_lag_(const rc_model* m);

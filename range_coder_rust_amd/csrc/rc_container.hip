@@ -626,8 +626,8 @@ rc_status rc_container2_pack(rc_ctx* ctx, const rc_model* m, const uint8_t* slot
   u32 nsym = 0, total = 0, inc = 0, lim = 0, per = 0, k_rows = 0, first_row = 0;
   const u32 *c_host = nullptr, *rows_dev = nullptr;
   const uint8_t* map_dev = nullptr;
-  // (RCB2 frames one map: a periodic order-1 set would lose its period)
-  if (rc_model_order1_period_(m) > 1) return RC_E_ARG;
+  // (RCB2 frames one map: a periodic order-1 set would lose its period, a lagged one its lag)
+  if (rc_model_order1_period_(m) > 1 || rc_model_order1_lag_(m) > 1) return RC_E_ARG;
   if (rc_model_order1_rows_(m, &rows_dev, &map_dev, &first_row, &k_rows, &nsym, &mdev)) {
     kind = 2;
   } else if (rc_model_wide_row_(m, &rows_dev, &nsym, &mdev)) {

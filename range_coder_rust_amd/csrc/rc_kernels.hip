@@ -108,6 +108,7 @@ struct rc_model {
   WideArgs wide;
   WidePlan wplan;
   O1Args o1;  // kind 4 (o1.period: 1, 2, 4 or 8)
+  u32 o1_lag;  // kind 4: 1, 2, 4 or 8 (rc_order1.h: no field of the kernels' O1Args)
   int device;
   int div;
   ModelArgs args;
@@ -141,6 +142,9 @@ bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** 
 }
 u32 rc_model_order1_period_(const rc_model* m) {
   return m && m->kind == RC_KIND_ORDER1 ? m->o1.period : 0u;
+}
+u32 rc_model_order1_lag_(const rc_model* m) {
+  return m && m->kind == RC_KIND_ORDER1 ? m->o1_lag : 0u;
 }
 
 namespace {
@@ -802,6 +806,7 @@ static rc_status set_build(rc_ctx* ctx, int kind, uint32_t n_models, uint32_t n_
     mm->o1.map = (const uint8_t*)(d + row_bytes + lut_bytes);
     mm->o1.first_row = first_row;
     mm->o1.period = period;
+    mm->o1_lag = 1;
   }
   *out = mm;
   return RC_OK;
@@ -948,15 +953,67 @@ rc_status rc_model_create_order1_set_periodic(rc_ctx* ctx, uint32_t n_models, ui
                    maps, period, first_row, out);
 }
 
+// what rc_model_create_order1_set_lagged accepts: a period and a lag of 1, 2, 4 or 8 (RC_E_ARG),
+// then the periodic rules (the map's rules do not depend on the lag)
+static rc_status order1_check_lagged(u32 n_models, u32 n_symbols, const u32* c, const u32* cum,
+                                     u32 total, u32 period, u32 lag, const uint8_t* ctx_map,
+                                     u32 first_row) {
+  if (!ctx_map || !o1_period_ok(period) || !o1_lag_ok(lag)) return RC_E_ARG;
+  return order1_check_periodic(n_models, n_symbols, c, cum, total, period, ctx_map, first_row);
+}
+
+// rc_model_order1_check_lagged_ / rc_model_order1_plan_lagged_: the periodic hooks with a lag
+// (tests/test_lag_model.py).  The plan does not depend on the lag: a lagged set stages what the
+// periodic set of its (K, total, P) stages and keeps its contexts in registers.
+rc_status rc_model_order1_check_lagged_(uint32_t n_models, uint32_t n_symbols,
+                                        const uint32_t* c_freq, const uint32_t* cum_freq,
+                                        uint32_t total_freq, uint32_t period, uint32_t lag,
+                                        const uint8_t* ctx_map, uint32_t first_row) {
+  return order1_check_lagged(n_models, n_symbols, c_freq, cum_freq, total_freq, period, lag,
+                             ctx_map, first_row);
+}
+rc_status rc_model_order1_plan_lagged_(uint32_t n_models, uint32_t total_freq, uint32_t period,
+                                       uint32_t lag, uint32_t* out) {
+  if (!o1_lag_ok(lag)) return RC_E_ARG;
+  return rc_model_order1_plan_periodic_(n_models, total_freq, period, out);
+}
+
+rc_status rc_model_create_order1_set_lagged(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                            const uint32_t* c_freq, const uint32_t* cum_freq,
+                                            uint32_t total_freq, uint32_t period, uint32_t lag,
+                                            const uint8_t* ctx_map, uint32_t first_row,
+                                            rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !ctx_map || !out) return RC_E_ARG;
+  *out = nullptr;
+  if (!o1_period_ok(period) || !o1_lag_ok(lag)) return RC_E_ARG;
+  // (lag 1: the periodic call itself, so the two cannot drift apart)
+  if (lag == 1)
+    return rc_model_create_order1_set_periodic(ctx, n_models, n_symbols, c_freq, cum_freq,
+                                               total_freq, period, ctx_map, first_row, out);
+  const rc_status ok = order1_check_lagged(n_models, n_symbols, c_freq, cum_freq, total_freq,
+                                           period, lag, ctx_map, first_row);
+  if (ok != RC_OK) return ok;
+  SetPlan plan;
+  rc_order1_plan(n_models, total_freq, period, &plan);
+  // the kernels stage 256 entries per slice: a symbol past the alphabet maps to row 0
+  uint8_t maps[O1_MAX_PERIOD * 256] = {0};
+  for (u32 ph = 0; ph < period; ++ph)
+    memcpy(maps + 256 * ph, ctx_map + (size_t)ph * n_symbols, n_symbols);
+  const rc_status st = set_build(ctx, RC_KIND_ORDER1, n_models, n_symbols, c_freq, cum_freq,
+                                 total_freq, plan, maps, period, first_row, out);
+  if (st == RC_OK) (*out)->o1_lag = lag;
+  return st;
+}
+
 rc_status rc_encode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,
                                  const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
                                  const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
   return batch_call(ctx, o1, 1u << RC_KIND_ORDER1, true, n_chunks,
                     syms && sym_off && out && out_off && out_len && flags,
                     "order-1 encode launch", [&] {
-                      return rc_order1_encode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div,
-                                                     o1->plan, syms, sym_off, n_chunks, out,
-                                                     out_off, out_len, flags);
+                      return rc_order1_encode_launch(ctx->cur, ctx->knobs, o1->o1, o1->o1_lag,
+                                                     o1->div, o1->plan, syms, sym_off, n_chunks,
+                                                     out, out_off, out_len, flags);
                     });
 }
 
@@ -967,9 +1024,9 @@ rc_status rc_decode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t*
   return batch_call(ctx, o1, 1u << RC_KIND_ORDER1, true, n_chunks,
                     code && code_off && code_len && syms_out && sym_off && flags,
                     "order-1 decode launch", [&] {
-                      return rc_order1_decode_launch(ctx->cur, ctx->knobs, o1->o1, o1->div,
-                                                     o1->plan, code, code_off, code_len, syms_out,
-                                                     sym_off, n_chunks, flags);
+                      return rc_order1_decode_launch(ctx->cur, ctx->knobs, o1->o1, o1->o1_lag,
+                                                     o1->div, o1->plan, code, code_off, code_len,
+                                                     syms_out, sym_off, n_chunks, flags);
                     });
 }
 

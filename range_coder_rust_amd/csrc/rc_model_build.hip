@@ -278,106 +278,11 @@ __global__ __launch_bounds__(256) void k_histogram_order1(
 #define O1P_WORDS (O1P_ROWS * 256u + 256u)        // the slice's counters, then the first symbols'
 #define O1P_LDS (4u * O1P_WORDS)
 
-template <bool PER>
-__global__ __launch_bounds__(O1P_WG) void k_histogram_pairs(
-    const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
-    u64* __restrict__ pair, u64* __restrict__ first, u32 period) {
-  extern __shared__ u32 s_pp[];
-  const u32 tid = threadIdx.x;
-  const u32 P = PER ? period : 1u, pm = P - 1;
-  const u32 slices = O1P_SLICES * P;
-  const u32 g = blockIdx.x % slices, w = blockIdx.x / slices;
-  const u32 G = gridDim.x / slices;
-  const u32 ph = g / O1P_SLICES;
-  const u32 base = (g % O1P_SLICES) * O1P_ROWS;  // the slice's first context
-  const bool do_first = first && g == 0;
-  RC_VGPR_FLOOR_48();
-  if (!pair && !do_first) return;  // (workgroup-uniform)
-  u32* const s_first = s_pp + O1P_ROWS * 256u;
-  for (u32 j = tid; j < O1P_WORDS; j += O1P_WG) s_pp[j] = 0;
-  __syncthreads();
-  auto flush = [&]() {
-    __syncthreads();
-    if (pair) {
-      for (u32 j = tid; j < O1P_ROWS * 256u; j += O1P_WG) {
-        const u32 v = s_pp[j];
-        if (v) {
-          atomicAdd(reinterpret_cast<unsigned long long*>(pair + ((u64)ph * 256u + base) * 256u + j),
-                    (unsigned long long)v);
-          s_pp[j] = 0;
-        }
-      }
-    }
-    if (do_first && tid < 256) {
-      const u32 v = s_first[tid];
-      if (v) {
-        atomicAdd(reinterpret_cast<unsigned long long*>(first + tid), (unsigned long long)v);
-        s_first[tid] = 0;
-      }
-    }
-    __syncthreads();
-  };
-  u64 pending = 0;  // symbols counted since the last flush (workgroup-uniform)
-  const u32 sub = tid / O1P_SUB, t = tid % O1P_SUB;
-  // a round: O1P_Q consecutive chunks, one per O1P_SUB lanes.  Every thread reads the round's
-  // lengths, so the budget and the flush (which has barriers) stay workgroup-uniform while the
-  // sub-groups walk chunks of different lengths.
-  for (u32 k0 = w * O1P_Q; k0 < n_chunks; k0 += G * O1P_Q) {
-    u64 len[O1P_Q], nmax = 0;
-#pragma unroll
-    for (u32 q = 0; q < O1P_Q; ++q) {
-      len[q] = k0 + q < n_chunks ? sym_off[k0 + q + 1] - sym_off[k0 + q] : 0;
-      nmax = len[q] > nmax ? len[q] : nmax;
-    }
-    const u32 k = k0 + sub;
-    const u64 s0 = k < n_chunks ? sym_off[k] : 0, n = k < n_chunks ? sym_off[k + 1] - s0 : 0;
-    const uint8_t* p = syms + s0;
-    for (u64 b0 = 0; b0 < nmax; b0 += O1P_SEG) {
-      u64 cnt = 0;  // at most O1P_Q * O1P_SEG = 2^31
-#pragma unroll
-      for (u32 q = 0; q < O1P_Q; ++q)
-        cnt += len[q] > b0 ? (len[q] - b0 < O1P_SEG ? len[q] - b0 : O1P_SEG) : 0;
-      if (pending + cnt > 0xFFFFFFFFull) {
-        flush();
-        pending = 0;
-      }
-      pending += cnt;
-      if (b0 >= n) continue;
-      const u64 b1 = n - b0 < O1P_SEG ? n : b0 + O1P_SEG;
-      if (!pair) {  // first symbols only
-        if (b0 == 0 && t == 0) atomicAdd(&s_first[p[0]], 1u);
-        continue;
-      }
-      for (u64 i = b0 + 16ull * t; i < b1; i += 16ull * O1P_SUB) {
-        // the previous symbol relative to the slice; a chunk's first symbol has none (chunk
-        // boundaries reset the context) and is counted in the first-symbol histogram
-        u32 rel = i ? (u32)p[i - 1] - base : 0x80000000u;
-        if (i == 0 && do_first) atomicAdd(&s_first[p[0]], 1u);
-        if (i + 16 <= b1) {
-          const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
-          const u32 ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const u32 s = (ws[q] >> (8 * j)) & 255u;
-              if (((u32)(4 * q + j) & pm) == ph && rel < O1P_ROWS)
-                atomicAdd(&s_pp[rel * 256u + s], 1u);
-              rel = s - base;
-            }
-          }
-        } else {
-          for (u64 j = i; j < b1; ++j) {
-            const u32 s = p[j];
-            if (((u32)j & pm) == ph && rel < O1P_ROWS) atomicAdd(&s_pp[rel * 256u + s], 1u);
-            rel = s - base;
-          }
-        }
-      }
-    }
-  }
-  flush();
-}
+// (the source: rc_hist_pairs.inc, once for lag 1 and once for the lagged kernels)
+#include "rc_hist_pairs.inc"
+#define O1C_LAGGED
+#include "rc_hist_pairs.inc"
+#undef O1C_LAGGED
 
 // k_ideal_bits_order1: per chunk the sum of icl[row_i][sym_i] over its symbols, row_0 =
 // first_row and row_i = map[sym[i-1]], straight from the symbols: no histogram and no atomics.
@@ -399,59 +304,11 @@ __global__ __launch_bounds__(O1P_WG) void k_histogram_pairs(
 // byte before its first pairs with phase 0: only the staged map (P x 256 B) and its index change;
 // the sums, their order and so the accuracy bound are the same.  Without PER, `period` is not
 // read (P = 1: every map index is the symbol).
-template <bool PER>
-__global__ __launch_bounds__(1024) void k_ideal_bits_order1(
-    const double* __restrict__ icl, const uint8_t* __restrict__ map, u32 first_row, u32 K,
-    const uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_chunks,
-    double* __restrict__ bits, u32 period) {
-  extern __shared__ double s_o1i[];
-  uint8_t* const s_map = reinterpret_cast<uint8_t*>(s_o1i + K * 256u);
-  const u32 lane = threadIdx.x & 63, waves = blockDim.x >> 6, pm = PER ? period - 1 : 0u;
-  const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (u32 j = threadIdx.x; j < K * 256u; j += blockDim.x) s_o1i[j] = icl[j];
-  // (one map: a workgroup has 256 lanes or more)
-  if (PER) {
-    for (u32 j = threadIdx.x; j < period * 256u; j += blockDim.x) s_map[j] = map[j];
-  } else if (threadIdx.x < 256) {
-    s_map[threadIdx.x] = map[threadIdx.x];
-  }
-  __syncthreads();
-  const u32 nw = gridDim.x * waves;
-  for (u32 k = blockIdx.x * waves + wave; k < n_chunks; k += nw) {
-    const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
-    const uint8_t* p = syms + s0;
-    double acc = 0.0;
-    for (u64 i = 16ull * lane; i < n; i += 16ull * 64) {
-      u32 row = i ? (u32)s_map[p[i - 1]] : first_row;  // chunk boundaries reset the context
-      if (i + 16 <= n) {
-        const u32x4 v = *(const __attribute__((address_space(1))) u32x4_h1*)(p + i);
-        const u32 ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const u32 s = (ws[q] >> (8 * j)) & 255u;
-            acc += s_o1i[row * 256u + s];
-            row = s_map[(((u32)(4 * q + j + 1) & pm) << 8) + s];
-          }
-        }
-      } else {
-        for (u64 j = i; j < n; ++j) {
-          const u32 s = p[j];
-          acc += s_o1i[row * 256u + s];
-          row = s_map[((((u32)j + 1u) & pm) << 8) + s];
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-      const u64 x = (u64)__double_as_longlong(acc);
-      const u64 y = ((u64)(u32)__shfl_xor((int)hi32(x), o) << 32) | (u32)__shfl_xor((int)(u32)x, o);
-      acc += __longlong_as_double((long long)y);
-    }
-    if (lane == 0) bits[k] = acc;
-  }
-}
+// (the source: rc_ideal_bits_order1.inc, once for lag 1 and once for the lagged kernels)
+#include "rc_ideal_bits_order1.inc"
+#define O1C_LAGGED
+#include "rc_ideal_bits_order1.inc"
+#undef O1C_LAGGED
 
 // per chunk: bits = sum_i hist[i] * icl[i] in f64 (icl[i] = +inf for c_i == 0: the reference's
 // ideal_code_length returns Err there, pmodel.rs:16-18).  One wave per chunk: lane L reads bins
@@ -1005,12 +862,13 @@ struct DevSet {
 };
 }  // namespace
 
-// rc_histogram_pairs (PER = false, period 1) and rc_histogram_pairs_periodic (PER = true, period
-// 1 included): each call keeps its own instantiation of the kernel
-template <bool PER>
-static rc_status histogram_pairs(rc_ctx* ctx, u32 period, const uint8_t* syms,
-                                 const uint64_t* sym_off, uint32_t n_chunks, uint64_t* pair_hist,
-                                 uint64_t* first_hist) {
+// rc_histogram_pairs (PER = false, period 1), rc_histogram_pairs_periodic (PER = true, period 1
+// included) and rc_histogram_pairs_lagged (one kernel per lag): each call keeps its own
+// instantiation of the kernel
+template <class Kern>
+static rc_status histogram_pairs_launch(Kern kern, rc_ctx* ctx, u32 period, const uint8_t* syms,
+                                        const uint64_t* sym_off, uint32_t n_chunks,
+                                        uint64_t* pair_hist, uint64_t* first_hist) {
   hipStream_t s;
   int dev;
   if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
@@ -1022,17 +880,23 @@ static rc_status histogram_pairs(rc_ctx* ctx, u32 period, const uint8_t* syms,
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return RC_E_DEVICE;
-  if (set_allow_lds(reinterpret_cast<const void*>(k_histogram_pairs<PER>)) != hipSuccess)
-    return RC_E_DEVICE;
+  if (set_allow_lds(reinterpret_cast<const void*>(kern)) != hipSuccess) return RC_E_DEVICE;
   // as many workgroups as the CUs hold (their LDS and 32 waves each), in O1P_SLICES * P groups
   // that stride over the chunks side by side
   const u32 slices = O1P_SLICES * period;
   const u32 per_cu = std::max(1u, std::min(163840u / O1P_LDS, 2048u / O1P_WG));
   const u32 groups =
       std::max(1u, std::min<u32>((n_chunks + O1P_Q - 1) / O1P_Q, (u32)cus * per_cu / slices));
-  hipLaunchKernelGGL(k_histogram_pairs<PER>, dim3(groups * slices), dim3(O1P_WG), O1P_LDS, s, syms,
-                     sym_off, n_chunks, pair_hist, first_hist, period);
+  hipLaunchKernelGGL(kern, dim3(groups * slices), dim3(O1P_WG), O1P_LDS, s, syms, sym_off,
+                     n_chunks, pair_hist, first_hist, period);
   return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+}
+template <bool PER>
+static rc_status histogram_pairs(rc_ctx* ctx, u32 period, const uint8_t* syms,
+                                 const uint64_t* sym_off, uint32_t n_chunks, uint64_t* pair_hist,
+                                 uint64_t* first_hist) {
+  return histogram_pairs_launch(k_histogram_pairs<PER>, ctx, period, syms, sym_off, n_chunks,
+                                pair_hist, first_hist);
 }
 
 extern "C" {
@@ -1100,6 +964,26 @@ rc_status rc_histogram_pairs_periodic(rc_ctx* ctx, uint32_t period, const uint8_
   return histogram_pairs<true>(ctx, period, syms, sym_off, n_chunks, pair_hist, first_hist);
 }
 
+rc_status rc_histogram_pairs_lagged(rc_ctx* ctx, uint32_t period, uint32_t lag,
+                                    const uint8_t* syms, const uint64_t* sym_off,
+                                    uint32_t n_chunks, uint64_t* pair_hist, uint64_t* first_hist) {
+  switch (lag) {
+    case 1:
+      return rc_histogram_pairs_periodic(ctx, period, syms, sym_off, n_chunks, pair_hist,
+                                         first_hist);
+    case 2:
+      return histogram_pairs_launch(k_histogram_pairs_lag<2>, ctx, period, syms, sym_off, n_chunks,
+                                    pair_hist, first_hist);
+    case 4:
+      return histogram_pairs_launch(k_histogram_pairs_lag<4>, ctx, period, syms, sym_off, n_chunks,
+                                    pair_hist, first_hist);
+    case 8:
+      return histogram_pairs_launch(k_histogram_pairs_lag<8>, ctx, period, syms, sym_off, n_chunks,
+                                    pair_hist, first_hist);
+  }
+  return RC_E_ARG;
+}
+
 rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,
                                const uint64_t* sym_off, uint32_t n_chunks, double* bits) {
   hipStream_t s;
@@ -1141,7 +1025,12 @@ rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* s
   double* d = nullptr;
   if (hipMallocAsync((void**)&d, icl_bytes, s) != hipSuccess) return RC_E_DEVICE;
   const u32 period = rc_model_order1_period_(o1);  // (> 1: map_dev holds `period` slices)
-  const auto kern = period > 1 ? k_ideal_bits_order1<true> : k_ideal_bits_order1<false>;
+  const u32 lag = rc_model_order1_lag_(o1);  // (> 1: the kernel of that lag, whatever the period)
+  const auto kern = lag == 2   ? k_ideal_bits_order1_lag<2>
+                    : lag == 4 ? k_ideal_bits_order1_lag<4>
+                    : lag == 8 ? k_ideal_bits_order1_lag<8>
+                    : period > 1 ? k_ideal_bits_order1<true>
+                                 : k_ideal_bits_order1<false>;
   if (hipMemcpyAsync(d, icl, icl_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
       set_allow_lds(reinterpret_cast<const void*>(kern)) != hipSuccess) {
     (void)hipFreeAsync(d, s);

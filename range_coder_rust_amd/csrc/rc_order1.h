@@ -33,6 +33,15 @@ static inline bool o1_period_ok(u32 period) {
 // leaves the plan zeroed.
 void rc_order1_plan(u32 n_models, u32 total, u32 period, SetPlan* p);
 
+// Lagged sets (rc_model_create_order1_set_lagged): the context is the symbol D
+// positions back, row_i = ctx_map[(i mod P) * n_symbols + sym[i-D]] for i >= D and first_row for
+// i < D, D in {1, 2, 4, 8} whatever P.  D == 1 is the set above in every respect.  The lag is a
+// compile-time constant of the kernels and no field of O1Args (the arguments of the lag-1 kernels
+// stay as they are): the model keeps it and hands it to the launchers.  A lagged set stages the
+// maps as a periodic set does and carries D contexts in registers, so its plan is the plan of its
+// (K, total, P).
+static inline bool o1_lag_ok(u32 lag) { return o1_period_ok(lag); }
+
 struct O1Args {
   SetArgs s;           // the rows and buckets, built for rc_order1_plan's dec_bits
   const uint8_t* map;  // [period][256] rows (device): slice ph = the map of the symbols i with
@@ -41,11 +50,25 @@ struct O1Args {
   u32 period;          // 1, 2, 4 or 8 (> 1: the launchers take the kernels that stage every slice)
 };
 
-hipError_t rc_order1_encode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a, int div,
-                                   const SetPlan& p, const uint8_t* syms, const u64* sym_off,
-                                   u32 n_chunks, uint8_t* out, const u64* out_off, u64* out_len,
-                                   u32* flags);
-hipError_t rc_order1_decode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a, int div,
-                                   const SetPlan& p, const uint8_t* code, const u64* code_off,
-                                   const u64* code_len, uint8_t* syms_out, const u64* sym_off,
-                                   u32 n_chunks, u32* flags);
+// the launchers of one lag > 1 each, defined by rc_order1_lag{2,4,8}.hip (rc_order1_lag.inc)
+template <int LAG>
+hipError_t rc_order1_encode_launch_lag(hipStream_t stream, const RcKnobs& k, const O1Args& a,
+                                       int div, const SetPlan& p, const uint8_t* syms,
+                                       const u64* sym_off, u32 n_chunks, uint8_t* out,
+                                       const u64* out_off, u64* out_len, u32* flags);
+template <int LAG>
+hipError_t rc_order1_decode_launch_lag(hipStream_t stream, const RcKnobs& k, const O1Args& a,
+                                       int div, const SetPlan& p, const uint8_t* code,
+                                       const u64* code_off, const u64* code_len,
+                                       uint8_t* syms_out, const u64* sym_off, u32 n_chunks,
+                                       u32* flags);
+
+// lag: the set's (1: the kernels of the period alone; else the call goes to the lag's unit)
+hipError_t rc_order1_encode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a, u32 lag,
+                                   int div, const SetPlan& p, const uint8_t* syms,
+                                   const u64* sym_off, u32 n_chunks, uint8_t* out,
+                                   const u64* out_off, u64* out_len, u32* flags);
+hipError_t rc_order1_decode_launch(hipStream_t stream, const RcKnobs& k, const O1Args& a, u32 lag,
+                                   int div, const SetPlan& p, const uint8_t* code,
+                                   const u64* code_off, const u64* code_len, uint8_t* syms_out,
+                                   const u64* sym_off, u32 n_chunks, u32* flags);

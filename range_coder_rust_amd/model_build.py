@@ -13,7 +13,8 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
                                   context class, the previous symbol picking the class (HIP)
   build_order1_set(syms, sym_off, ctx_map)   those counts -> Order1ModelSet, in one call
   histogram_pairs_periodic(syms, sym_off, P) rc_histogram_pairs_periodic: the pair histogram per
-                                  position in a record of P bytes (HIP)
+                                  position in a record of P bytes (HIP); lag=D takes the pairs
+                                  D symbols apart (rc_histogram_pairs_lagged)
   histogram_pairs(syms, sym_off)  rc_histogram_pairs: the full 256 x 256 pair histogram and the
                                   histogram of the chunks' first symbols (HIP)
   cluster_contexts(pair, first, K)           rc_cluster_contexts: those counts -> a context map
@@ -142,7 +143,8 @@ def _ctx_maps256(ctx_map, period):
 
 def _class_counts(pair, first, maps, first_row, n_models):
     """The counts of the rows of a periodic set from periodic pair counts (host): row j collects
-    pair[ph][p] of every (ph, p) with maps[ph][p] == j, and first_row the first symbols."""
+    pair[ph][p] of every (ph, p) with maps[ph][p] == j, and first_row the first symbols (at a
+    lag: the first `lag` symbols of every chunk, as histogram_pairs_periodic counts them)."""
     counts = np.zeros((n_models, 256), np.uint64)
     for ph in range(len(pair)):
         np.add.at(counts, maps[ph].astype(np.int64), pair[ph].astype(np.uint64))
@@ -151,24 +153,27 @@ def _class_counts(pair, first, maps, first_row, n_models):
 
 
 def build_order1_set(syms, sym_off, ctx_map, first_row=0, target_total=1 << 16, n_symbols=256,
-                     n_models=None, ctx=None, period=1):
+                     n_models=None, ctx=None, period=1, lag=1):
     """Pair counts of the batch on the GPU, then an Order1ModelSet of the rows quantised from
     them (every symbol kept encodable in every row).  period > 1: ctx_map is [period, n] and
-    the rows' counts are summed on the host from histogram_pairs_periodic's."""
+    the rows' counts are summed on the host from histogram_pairs_periodic's.  lag > 1: the pairs
+    are taken at that distance (a flat map is accepted at period 1), counted the same way."""
     ctx = ctx or default_context(syms.device.index)
-    period = int(period)
-    if period != 1:
+    period, lag = int(period), int(lag)
+    if period != 1 or lag != 1:
+        if period == 1 and np.asarray(ctx_map).ndim == 1:
+            ctx_map = np.asarray(ctx_map)[None]
         maps = _ctx_maps256(ctx_map, period)
         K = int(n_models) if n_models is not None else max(int(maps.max()), int(first_row)) + 1
         if not 1 <= K <= N.MAX_SET_MODELS or int(maps.max()) >= K or not 0 <= int(first_row) < K:
             raise ValueError(f"ctx_map and first_row must name rows 0..{K - 1} of at most "
                              f"{N.MAX_SET_MODELS}")
-        pair, first = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx)
+        pair, first = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx, lag=lag)
         counts = _class_counts(pair.cpu().numpy(), first.cpu().numpy(), maps, int(first_row), K)
         if n_symbols < 256 and counts[:, n_symbols:].any():
             raise ValueError(f"symbols >= {n_symbols} present")
         return Order1ModelSet.from_counts(counts[:, :n_symbols], maps[:, :n_symbols], first_row,
-                                          target_total, ctx=ctx, period=period)
+                                          target_total, ctx=ctx, period=period, lag=lag)
     hist = histogram_order1(syms, sym_off, ctx_map, first_row, n_models=n_models, ctx=ctx)
     counts = hist.cpu().numpy().astype(np.uint64)
     if n_symbols < 256 and counts[:, n_symbols:].any():
@@ -203,19 +208,27 @@ def histogram_pairs(syms, sym_off, pair_hist=None, first_hist=None, ctx=None):
     return pair_hist, first_hist
 
 
-def histogram_pairs_periodic(syms, sym_off, period, pair_hist=None, first_hist=None, ctx=None):
+def histogram_pairs_periodic(syms, sym_off, period, pair_hist=None, first_hist=None, ctx=None,
+                             lag=1):
     """rc_histogram_pairs_periodic on torch tensors (async, torch's current stream).
 
     Returns (pair_hist, first_hist): int64[period, 256, 256], [ph][p][s] = the positions i >= 1
     of a chunk with i % period == ph, sym[i-1] = p and sym[i] = s (i counted from the chunk's
     start), and int64[256] as histogram_pairs gives it.  Chunk boundaries reset the context.
-    Given arrays are added into.  period: 1, 2, 4 or 8."""
+    Given arrays are added into.  period: 1, 2, 4 or 8.
+
+    lag (1, 2, 4 or 8; rc_histogram_pairs_lagged for lag > 1): the pairs are taken at that
+    distance, [ph][p][s] = the positions i >= lag with sym[i-lag] = p, and first_hist counts the
+    positions i < lag of every chunk, so that the two sum to the number of symbols."""
     torch = _torch()
     _check_dev(syms, "syms", (torch.uint8,))
     _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
     period = int(period)
     if period not in (1, 2, 4, 8):
         raise ValueError("period must be 1, 2, 4 or 8")
+    lag = int(lag)
+    if lag not in (1, 2, 4, 8):
+        raise ValueError("lag must be 1, 2, 4 or 8")
     ctx = ctx or default_context(syms.device.index)
     n = sym_off.numel() - 1
     for name, t, shape in (("pair_hist", pair_hist, (period, 256, 256)),
@@ -229,6 +242,12 @@ def histogram_pairs_periodic(syms, sym_off, period, pair_hist=None, first_hist=N
     if first_hist is None:
         first_hist = torch.zeros(256, dtype=torch.int64, device=syms.device)
     ctx.bind_stream()
+    if lag != 1:
+        N.check(ctx._lib.rc_histogram_pairs_lagged(ctx.handle, period, lag, _ptr(syms),
+                                                   _ptr(sym_off), n, _ptr(pair_hist),
+                                                   _ptr(first_hist)),
+                "rc_histogram_pairs_lagged")
+        return pair_hist, first_hist
     N.check(ctx._lib.rc_histogram_pairs_periodic(ctx.handle, period, _ptr(syms), _ptr(sym_off),
                                                  n, _ptr(pair_hist), _ptr(first_hist)),
             "rc_histogram_pairs_periodic")
@@ -299,7 +318,7 @@ def cluster_contexts_joint(pair_hist, first_hist, n_models=64, n_symbols=256, ct
 
 
 def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=256, ctx=None,
-                   period=1, joint=False):
+                   period=1, joint=False, lag=1):
     """An Order1ModelSet fitted to the batch: pair counts on the GPU (histogram_pairs), a context
     map of at most n_models classes from them (cluster_contexts), the classes' counts on the GPU
     (histogram_order1 with the map found) and their quantised rows.  The set's ctx_map and
@@ -318,28 +337,35 @@ def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=2
     pair counts where they lie: all the (phase, context) items at once, so the n_models rows are
     shared by the phases as the data asks, and n_models < period is allowed.  The classes'
     counts are summed on the host from the pair counts as above.  At period 1 only the
-    clustering moves to the device; the rest is as without `joint`."""
-    period = int(period)
+    clustering moves to the device; the rest is as without `joint`.
+
+    lag > 1 (2, 4 or 8) fits a lagged set: the pair counts are taken at that
+    distance (histogram_pairs_periodic with the lag), the start-of-chunk item is the first `lag`
+    symbols of every chunk, and the clustering, the class counts and the rows are those of a
+    periodic fit, whatever the period (period 1 included).  lag=1 is the code above unchanged."""
+    period, lag = int(period), int(lag)
     if period not in (1, 2, 4, 8):
         raise ValueError("period must be 1, 2, 4 or 8")
+    if lag not in (1, 2, 4, 8):
+        raise ValueError("lag must be 1, 2, 4 or 8")
     if int(n_models) < period and not joint:
         raise ValueError(f"n_models = {n_models} leaves a phase of period {period} no row")
     ctx = ctx or default_context(syms.device.index)
-    if joint and period != 1:
-        pair_t, first_t = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx)
+    if joint and (period != 1 or lag != 1):
+        pair_t, first_t = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx, lag=lag)
         cm, first_row, k, _ = cluster_contexts_joint(pair_t, first_t, n_models, n_symbols, ctx=ctx)
         maps = np.zeros((period, 256), np.uint8)
         maps[:, :cm.shape[1]] = cm
         counts = _class_counts(pair_t.cpu().numpy(), first_t.cpu().numpy(), maps, first_row, k)
         return Order1ModelSet.from_counts(counts[:, :n_symbols], maps[:, :n_symbols], first_row,
-                                          target_total, ctx=ctx, period=period)
+                                          target_total, ctx=ctx, period=period, lag=lag)
     if joint:
         pair, first = histogram_pairs(syms, sym_off, ctx=ctx)
         cm, first_row, k, _ = cluster_contexts_joint(pair, first, n_models, n_symbols, ctx=ctx)
         return build_order1_set(syms, sym_off, cm, first_row, target_total, n_symbols, n_models=k,
                                 ctx=ctx)
-    if period != 1:
-        pair_t, first_t = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx)
+    if period != 1 or lag != 1:
+        pair_t, first_t = histogram_pairs_periodic(syms, sym_off, period, ctx=ctx, lag=lag)
         pair, first = pair_t.cpu().numpy(), first_t.cpu().numpy()
         maps = np.zeros((period, 256), np.uint8)
         first_row, rows = 0, 0
@@ -354,7 +380,7 @@ def fit_order1_set(syms, sym_off, n_models=64, target_total=1 << 16, n_symbols=2
             rows += k
         counts = _class_counts(pair, first, maps, first_row, rows)
         return Order1ModelSet.from_counts(counts[:, :n_symbols], maps[:, :n_symbols], first_row,
-                                          target_total, ctx=ctx, period=period)
+                                          target_total, ctx=ctx, period=period, lag=lag)
     pair, first = histogram_pairs(syms, sym_off, ctx=ctx)
     cm, first_row, k, _ = cluster_contexts(pair.cpu().numpy(), first.cpu().numpy(), n_models,
                                            n_symbols)

@@ -40,7 +40,7 @@ WIDE1 = os.path.join(ROOT, "variants", "librc_guard_wide1.so")
 SPAN16 = os.path.join(ROOT, "variants", "librc_guard_span16.so")
 MUTANTS = os.path.join(ROOT, "profiles", "ring_tight", "mutants.json")
 DECODERS = ["rc_decode_pow2.hip", "rc_decode_magic.hip", "rc_indexed.hip", "rc_order1.hip",
-            "rc_wide.hip"]
+            "rc_order1_lag2.hip", "rc_order1_lag4.hip", "rc_order1_lag8.hip", "rc_wide.hip"]
 F_RING_GUARD = 0x100
 
 
