@@ -548,15 +548,9 @@ class Order1ModelSet:
         self._handle = None
         tables = (self.n_models, self.n_symbols, ctypes.c_void_p(c.ctypes.data),
                   ctypes.c_void_p(cum.ctypes.data), ctypes.c_uint32(self.total & 0xFFFFFFFF))
-        where = (ctypes.c_void_p(self.ctx_map.ctypes.data), ctypes.c_uint32(self.first_row))
-        # (period 1 and lag 1 go through the calls they always did)
-        if lag != 1:
-            rc = N.load().rc_model_order1_check_lagged_(*tables, ctypes.c_uint32(period),
-                                                        ctypes.c_uint32(lag), *where)
-        else:
-            rc = (N.load().rc_model_order1_check_(*tables, *where) if period == 1 else
-                  N.load().rc_model_order1_check_periodic_(*tables, ctypes.c_uint32(period),
-                                                           *where))
+        rc = N.load().rc_model_order1_check_lagged_(
+            *tables, ctypes.c_uint32(period), ctypes.c_uint32(lag),
+            ctypes.c_void_p(self.ctx_map.ctypes.data), ctypes.c_uint32(self.first_row))
         if rc != N.RC_OK or self.total > 0xFFFFFFFF:
             raise ValueError(
                 f"order-1 set rejected: need 1..{N.MAX_SET_MODELS} rows of 1..256 symbols, one "
@@ -592,22 +586,13 @@ class Order1ModelSet:
     def handle(self):
         if self._handle is None:
             h = ctypes.c_void_p()
-            tables = (self.ctx.handle, self.n_models, self.n_symbols,
-                      ctypes.c_void_p(self.c.ctypes.data), ctypes.c_void_p(self.cum.ctypes.data),
-                      ctypes.c_uint32(self.total))
-            where = (ctypes.c_void_p(self.ctx_map.ctypes.data), ctypes.c_uint32(self.first_row),
-                     ctypes.byref(h))
-            if self.lag != 1:
-                N.check(self.ctx._lib.rc_model_create_order1_set_lagged(
-                    *tables, ctypes.c_uint32(self.period), ctypes.c_uint32(self.lag), *where),
-                    "rc_model_create_order1_set_lagged")
-            elif self.period == 1:
-                N.check(self.ctx._lib.rc_model_create_order1_set(*tables, *where),
-                        "rc_model_create_order1_set")
-            else:
-                N.check(self.ctx._lib.rc_model_create_order1_set_periodic(
-                    *tables, ctypes.c_uint32(self.period), *where),
-                    "rc_model_create_order1_set_periodic")
+            N.check(self.ctx._lib.rc_model_create_order1_set_lagged(
+                self.ctx.handle, self.n_models, self.n_symbols,
+                ctypes.c_void_p(self.c.ctypes.data), ctypes.c_void_p(self.cum.ctypes.data),
+                ctypes.c_uint32(self.total), ctypes.c_uint32(self.period),
+                ctypes.c_uint32(self.lag), ctypes.c_void_p(self.ctx_map.ctypes.data),
+                ctypes.c_uint32(self.first_row), ctypes.byref(h)),
+                "rc_model_create_order1_set_lagged")
             self._handle = h
         return self._handle
 

@@ -231,13 +231,6 @@ static __device__ __forceinline__ void gstore32(uint8_t* p, u32 v) { *(g_u32*)p 
 static __device__ __forceinline__ void gstore64(uint8_t* p, u64 v) { *(g_u64*)p = v; }
 static __device__ __forceinline__ void gstore128(uint8_t* p, u32x4 v) { *(g_u32x4*)p = v; }
 
-// A pinned host buffer of at least `bytes` (<= 1 MiB) for this host thread, grown on demand
-// (rc_kernels.hip).  Host <-> device transfers of small control data go through it: async
-// copies to and from pageable memory returned wrong bytes intermittently on this stack
-// (DESIGN.md §6), pinned ones are plain stream-ordered DMA.  Contents are the caller's until
-// its next call on the same thread.
-void* rc_pinned_scratch_(size_t bytes);
-
 // Adaptive order-0 model parameters (rc_model_create_adaptive)
 struct AdaptParams {
   u32 n;      // alphabet size (1..256)
@@ -275,28 +268,3 @@ struct RcKnobs {
   u64 stream_batch_bytes;  // RC_STREAM_BATCH_BYTES=n: the host pipeline's batch size (0: default)
   bool hist_hot;           // RC_HIST_HOT=0: the histogram without its ballot-counted hot symbol
 };
-RcKnobs rc_knobs_from_env();                      // rc_kernels.hip (rc_ctx_create only)
-// rc_resume.hip: ask the process's stream-service waves to leave before a batch launch (a
-// resident wave would hold the hardware queue its stream shares with the launch's)
-void rc_svc_yield_all_();
-const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx);  // rc_kernels.hip
-// rc_kernels.hip: true for a static model set (rc_model_create_static_set), which only the
-// indexed batch calls take; every other entry point that takes a model refuses it (RC_E_ARG)
-bool rc_model_is_set_(const rc_model* m);
-// likewise for a wide static model (rc_model_create_static_wide) and the wide batch calls
-bool rc_model_is_wide_(const rc_model* m);
-// likewise for an order-1 set (rc_model_create_order1_set) and the order-1 batch calls
-bool rc_model_is_order1_(const rc_model* m);
-// rc_kernels.hip: a wide static model's cum row (device memory: cum[0 .. n], cum[n] = total), its
-// alphabet size and its device; false for any other kind of model (rc_ideal_bits_wide)
-bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int* device);
-// rc_kernels.hip: an order-1 set's cum rows (device memory: [n_models][257], cum[0 .. 256] with
-// the entries from n_symbols on holding the total), its staged 256-entry map (device memory),
-// first_row, sizes and device; false for any other kind of model (rc_ideal_bits_order1).  A
-// periodic set's map is its `period` staged slices back to back.
-bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** map,
-                           u32* first_row, u32* n_models, u32* n_symbols, int* device);
-// the period of an order-1 set (1, 2, 4 or 8); 0 for any other kind of model
-u32 rc_model_order1_period_(const rc_model* m);
-// the lag of an order-1 set (1, 2, 4 or 8); 0 for any other kind of model
-u32 rc_model_order1_lag_(const rc_model* m);

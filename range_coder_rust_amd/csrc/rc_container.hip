@@ -19,7 +19,7 @@
 // and payload: it also frames order-1 sets and wide static models, and may carry one checksum
 // of the decoded symbols per chunk (k_chunk_checksum, HBM-bound).  RCB1's entry points and
 // kernels are unchanged by it.
-#include "rc_common.h"
+#include "rc_host.h"
 
 #include <string.h>
 
@@ -301,28 +301,7 @@ __global__ __launch_bounds__(SWG) void k_unpack_index(const u64* __restrict__ in
 // ------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------
-struct rc_ctx;
-struct rc_model;
-extern "C" {
-rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device);
-rc_status rc_model_describe_(const rc_model* m, int* kind, int* device, uint32_t* n_symbols,
-                             uint32_t* total, const uint32_t** c_host, uint32_t* increment,
-                             uint32_t* limit, uint32_t* period);
-}
-
 namespace {
-struct DevSet {
-  int prev = -1;
-  explicit DevSet(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DevSet() {
-    int now = -1;
-    if (prev >= 0 && hipGetDevice(&now) == hipSuccess && now != prev) (void)hipSetDevice(prev);
-  }
-};
-
 u64 hpad16(u64 v) { return (v + 15) & ~15ull; }
 
 struct Scratch {
@@ -384,20 +363,17 @@ rc_status rc_container_pack(rc_ctx* ctx, const rc_model* m, const uint8_t* slots
                             const uint64_t* slot_off_dev, const uint64_t* code_len_dev,
                             const uint64_t* sym_off_dev, uint32_t n_chunks, uint8_t* dst_dev,
                             uint64_t dst_cap, uint64_t* dst_len_host) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !m || !dst_len_host || n_chunks > RC_MAX_CHUNKS)
-    return RC_E_ARG;
+  if (!ctx || !m || !dst_len_host || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_chunks && (!slots_dev || !slot_off_dev || !code_len_dev || !sym_off_dev)) return RC_E_ARG;
   // (RCB1 frames single-table one-byte models only)
-  if (rc_model_is_set_(m) || rc_model_is_wide_(m) || rc_model_is_order1_(m)) return RC_E_ARG;
-  int kind, mdev;
-  u32 nsym, total, inc, lim, per;
-  const u32* c_host;
-  if (rc_model_describe_(m, &kind, &mdev, &nsym, &total, &c_host, &inc, &lim, &per) != RC_OK ||
-      mdev != dev)
-    return RC_E_ARG;
-  DevSet g(dev);
+  if (!rc_model_kind_ok(m, RC_KINDS_SINGLE) || m->device != dev) return RC_E_ARG;
+  const int kind = m->kind;
+  const u32 nsym = kind == 0 ? m->args.n : m->ap.n, total = m->args.total;
+  const u32 inc = m->ap.inc, lim = m->ap.limit, per = m->period;
+  const u32* const c_host = m->c_host;
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   const u64 index_off = RC_CONTAINER_HEADER_BYTES + (kind == 0 ? hpad16(4ull * nsym) : 0);
   const u64 payload_off = index_off + 16ull * n_chunks;
@@ -459,13 +435,13 @@ rc_status rc_container_pack(rc_ctx* ctx, const rc_model* m, const uint8_t* slots
 rc_status rc_container_offsets(rc_ctx* ctx, const uint8_t* container_dev,
                                const rc_container_info* info, uint64_t* code_off_dev,
                                uint64_t* code_len_dev, uint64_t* sym_off_dev) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !container_dev || !info) return RC_E_ARG;
+  if (!ctx || !container_dev || !info) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   const u32 n = (u32)info->n_chunks;
   if (info->n_chunks > RC_MAX_CHUNKS) return RC_E_BAD_CONTAINER;
   if (n && (!code_off_dev || !code_len_dev || !sym_off_dev)) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   const u64* index = reinterpret_cast<const u64*>(container_dev + info->index_off);
   const u32 nb = (n + SBLK - 1) / SBLK;
   // code_off needs n + 1 slots for the scan total: scratch, then copy the first n
@@ -551,13 +527,12 @@ extern "C" {
 rc_status rc_checksum_batch_grid_(rc_ctx* ctx, const void* data_dev, const uint64_t* off_dev,
                                   uint32_t n_chunks, uint32_t sym_bytes, uint32_t* sums_dev,
                                   uint32_t grid) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS ||
-      (sym_bytes != 1 && sym_bytes != 2) || grid > 65536)
+  if (!ctx || n_chunks > RC_MAX_CHUNKS || (sym_bytes != 1 && sym_bytes != 2) || grid > 65536)
     return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_chunks && (!data_dev || !off_dev || !sums_dev)) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   return checksum_launch(s, dev, data_dev, off_dev, n_chunks, sym_bytes, sums_dev, nullptr,
                          nullptr, grid) == hipSuccess
              ? RC_OK
@@ -616,30 +591,35 @@ rc_status rc_container2_pack(rc_ctx* ctx, const rc_model* m, const uint8_t* slot
                              const uint64_t* sym_off_dev, uint32_t n_chunks,
                              const uint32_t* sums_dev, uint8_t* dst_dev, uint64_t dst_cap,
                              uint64_t* dst_len_host) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !m || !dst_len_host || n_chunks > RC_MAX_CHUNKS)
-    return RC_E_ARG;
+  if (!ctx || !m || !dst_len_host || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_chunks && (!slots_dev || !slot_off_dev || !code_len_dev || !sym_off_dev)) return RC_E_ARG;
   // what the model is: kind, sizes, and where its table comes from
-  int kind = -1, mdev = -1;
+  int kind = m->kind;
   u32 nsym = 0, total = 0, inc = 0, lim = 0, per = 0, k_rows = 0, first_row = 0;
   const u32 *c_host = nullptr, *rows_dev = nullptr;
   const uint8_t* map_dev = nullptr;
-  // (RCB2 frames one map: a periodic order-1 set would lose its period, a lagged one its lag)
-  if (rc_model_order1_period_(m) > 1 || rc_model_order1_lag_(m) > 1) return RC_E_ARG;
-  if (rc_model_order1_rows_(m, &rows_dev, &map_dev, &first_row, &k_rows, &nsym, &mdev)) {
+  // (a static set is not among them: it has no index stream to frame)
+  if (!rc_model_kind_ok(m, RC_KINDS_SINGLE | 1u << RC_KIND_WIDE | 1u << RC_KIND_ORDER1))
+    return RC_E_ARG;
+  if (kind == RC_KIND_ORDER1) {
+    // (RCB2 frames one map: a periodic order-1 set would lose its period, a lagged one its lag)
+    if (m->o1.period > 1 || m->o1_lag > 1) return RC_E_ARG;
     kind = 2;
-  } else if (rc_model_wide_row_(m, &rows_dev, &nsym, &mdev)) {
+    rows_dev = m->o1.s.rows, map_dev = m->o1.map;
+    first_row = m->o1.first_row, k_rows = m->o1.s.k, nsym = m->o1.s.m.n;
+  } else if (kind == RC_KIND_WIDE) {
     kind = 3;
-  } else if (rc_model_describe_(m, &kind, &mdev, &nsym, &total, &c_host, &inc, &lim, &per) !=
-             RC_OK) {
-    return RC_E_ARG;  // (a static set: it has no index stream to frame)
+    rows_dev = m->wide.row, nsym = m->wide.m.n;
+  } else {
+    nsym = kind == 0 ? m->args.n : m->ap.n, total = m->args.total, c_host = m->c_host;
+    inc = m->ap.inc, lim = m->ap.limit, per = m->period;
   }
-  if (mdev != dev || nsym < 1 || nsym > (kind == 3 ? RC_MAX_WIDE_SYMBOLS : 256u) ||
+  if (m->device != dev || nsym < 1 || nsym > (kind == 3 ? RC_MAX_WIDE_SYMBOLS : 256u) ||
       (kind == 2 && (k_rows < 1 || k_rows > RC_MAX_SET_MODELS)))
     return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   const u64 index_off = RC_CONTAINER_HEADER_BYTES + c2_table_bytes((u32)kind, nsym, k_rows);
   const u64 sum_off = index_off + 16ull * n_chunks;
@@ -737,10 +717,10 @@ rc_status rc_container2_offsets(rc_ctx* ctx, const uint8_t* container_dev, const
 
 rc_status rc_container2_model(rc_ctx* ctx, const uint8_t* container_dev, const void* info2,
                               rc_model** out) {
-  hipStream_t s;
-  int dev;
   const rc_container2_info* in = c2_info(info2);
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !container_dev || !in || !out) return RC_E_ARG;
+  if (!ctx || !container_dev || !in || !out) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   *out = nullptr;
   const u32 n = in->n_symbols, k = in->kind == 2 ? in->n_models : 1;
   if (in->kind > 3 || n < 1 || n > (in->kind == 3 ? RC_MAX_WIDE_SYMBOLS : 256u) || k < 1 ||
@@ -751,7 +731,7 @@ rc_status rc_container2_model(rc_ctx* ctx, const uint8_t* container_dev, const v
     rc = rc_model_create_adaptive(ctx, n, in->increment, in->limit, in->period, out);
     return rc == RC_E_BAD_MODEL ? RC_E_BAD_CONTAINER : rc;
   }
-  DevSet g(dev);
+  DeviceGuard g(dev);
   char* pin = (char*)rc_pinned_scratch_(C2_PIN_BYTES);
   if (!pin) return RC_E_DEVICE;
   const u64 tbytes = in->index_off - in->table_off;
@@ -787,17 +767,17 @@ rc_status rc_container2_model(rc_ctx* ctx, const uint8_t* container_dev, const v
 rc_status rc_container2_verify(rc_ctx* ctx, const uint8_t* container_dev, const void* info2,
                                const void* syms_dev, const uint64_t* sym_off_dev,
                                uint64_t* first_bad_host) {
-  hipStream_t s;
-  int dev;
   const rc_container2_info* in = c2_info(info2);
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !container_dev || !in || !first_bad_host ||
-      in->n_chunks > RC_MAX_CHUNKS || (in->sym_bytes != 1 && in->sym_bytes != 2))
+  if (!ctx || !container_dev || !in || !first_bad_host || in->n_chunks > RC_MAX_CHUNKS ||
+      (in->sym_bytes != 1 && in->sym_bytes != 2))
     return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   const u32 n = (u32)in->n_chunks;
   *first_bad_host = n;
   if (!(in->flags & RC_CONTAINER2_F_CHECKSUMS) || !n) return RC_OK;
   if (!syms_dev || !sym_off_dev) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   Scratch sc(s);
   if (!sc.alloc(16)) return RC_E_DEVICE;
   u32* bad = (u32*)sc.p;

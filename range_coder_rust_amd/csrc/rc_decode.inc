@@ -863,8 +863,6 @@ bool symof_candidate(const RcKnobs& k, const ModelArgs& a, int sm) {
 }
 }  // namespace
 
-hipError_t set_allow_lds(const void* kernel);  // rc_indexed.hip: a whole CU's LDS as dynamic LDS
-
 #if RC_DEC_DIV == 0
 hipError_t rc_static_decode_launch_pow2(
 #else

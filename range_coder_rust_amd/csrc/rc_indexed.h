@@ -43,11 +43,9 @@ struct SetArgs {
   u32 tab_bytes;    // encoder: SetPlan::enc_tab
 };
 
-// shared with the wide coders (rc_wide.hip), whose workgroups are sized the same way:
-// set_allow_lds lets `kernel` take a whole CU's LDS as dynamic LDS; set_launch_lanes gives the
-// lanes per workgroup of a launch of n_chunks chunks (the plan's, or fewer so that a small launch
-// reaches every CU)
-hipError_t set_allow_lds(const void* kernel);
+// shared with the wide coders (rc_wide.hip), whose workgroups are sized the same way (as is
+// set_allow_lds, which rc_static.h declares): the lanes per workgroup of a launch of n_chunks
+// chunks (the plan's, or fewer so that a small launch reaches every CU)
 u32 set_launch_lanes(u32 plan_lanes, u32 n_chunks);
 
 hipError_t rc_set_encode_launch(hipStream_t stream, const RcKnobs& k, const SetArgs& a, int div,

@@ -1,9 +1,7 @@
 // rc_kernels.hip — host side of the static-model coder (contexts, models, launches) and the
-// synthetic workload generator.  The kernels: rc_encode.hip, rc_decode.inc (rc_static.h).
-#include "rc_static.h"
-#include "rc_indexed.h"
-#include "rc_order1.h"
-#include "rc_wide.h"
+// synthetic workload generator.  The kernels: rc_encode.hip, rc_decode.inc (rc_static.h).  The
+// context and the model themselves: rc_host.h.
+#include "rc_host.h"
 
 // ------------------------------------------------------------------------------------------
 // Synthetic workload generator (inputs for bench/tests, generated directly in HBM)
@@ -58,14 +56,6 @@ __global__ __launch_bounds__(WG) void k_synth_generic(u64 seed, const uint8_t* _
 #include <cmath>
 #include <vector>
 
-struct rc_ctx {
-  int device;
-  hipStream_t own;
-  hipStream_t cur;
-  uint8_t* inv;  // 64 KiB device scratch for rc_synth_fill's inverse CDF
-  RcKnobs knobs;  // read from the environment once, here (rc_common.h)
-};
-
 // The only place the library reads its environment (tests/test_abi.py checks that no other
 // source calls getenv): once per context, in rc_ctx_create.
 RcKnobs rc_knobs_from_env() {
@@ -89,78 +79,7 @@ RcKnobs rc_knobs_from_env() {
   return k;
 }
 
-const RcKnobs& rc_ctx_knobs_(const rc_ctx* ctx) { return ctx->knobs; }
-
-enum {
-  RC_KIND_STATIC = 0,
-  RC_KIND_ADAPTIVE = 1,
-  RC_KIND_SET = 2,
-  RC_KIND_WIDE = 3,
-  RC_KIND_ORDER1 = 4
-};
-
-struct rc_model {
-  int kind;  // 0 static, 1 adaptive, 2 static model set (rc_indexed.h: `set` and `plan`),
-             // 3 wide static model (rc_wide.h: `wide` and `wplan`), 4 order-1 set (rc_order1.h:
-             // `o1` and `plan`)
-  SetArgs set;
-  SetPlan plan;
-  WideArgs wide;
-  WidePlan wplan;
-  O1Args o1;  // kind 4 (o1.period: 1, 2, 4 or 8)
-  u32 o1_lag;  // kind 4: 1, 2, 4 or 8 (rc_order1.h: no field of the kernels' O1Args)
-  int device;
-  int div;
-  ModelArgs args;
-  void* dmem;
-  AdaptParams ap;      // kind 1
-  u32 c_host[256];     // kind 0: the c_freq snapshot (container tables, entropy reports)
-  u32 period;          // kind 1: as given
-  bool complete;       // kind 0: 256 symbols, every c_freq > 0 (no symbol the coder can reject)
-};
-
-bool rc_model_is_set_(const rc_model* m) { return m && m->kind == RC_KIND_SET; }
-bool rc_model_is_wide_(const rc_model* m) { return m && m->kind == RC_KIND_WIDE; }
-bool rc_model_is_order1_(const rc_model* m) { return m && m->kind == RC_KIND_ORDER1; }
-bool rc_model_wide_row_(const rc_model* m, const u32** row, u32* n_symbols, int* device) {
-  if (!m || m->kind != RC_KIND_WIDE) return false;
-  *row = m->wide.row;
-  *n_symbols = m->wide.m.n;
-  *device = m->device;
-  return true;
-}
-bool rc_model_order1_rows_(const rc_model* m, const u32** rows, const uint8_t** map,
-                           u32* first_row, u32* n_models, u32* n_symbols, int* device) {
-  if (!m || m->kind != RC_KIND_ORDER1) return false;
-  *rows = m->o1.s.rows;
-  *map = m->o1.map;
-  *first_row = m->o1.first_row;
-  *n_models = m->o1.s.k;
-  *n_symbols = m->o1.s.m.n;
-  *device = m->device;
-  return true;
-}
-u32 rc_model_order1_period_(const rc_model* m) {
-  return m && m->kind == RC_KIND_ORDER1 ? m->o1.period : 0u;
-}
-u32 rc_model_order1_lag_(const rc_model* m) {
-  return m && m->kind == RC_KIND_ORDER1 ? m->o1_lag : 0u;
-}
-
 namespace {
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    int now = -1;
-    if (prev >= 0 && hipGetDevice(&now) == hipSuccess && now != prev) (void)hipSetDevice(prev);
-  }
-};
 
 thread_local char g_last_error[256] = "";
 
@@ -347,7 +266,7 @@ template <class Launch>
 static rc_status batch_call(rc_ctx* ctx, const rc_model* m, u32 kinds, bool aligned,
                             uint32_t n_chunks, bool arrays, const char* what, Launch launch) {
   if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (!((kinds >> m->kind) & 1u) || !aligned) return RC_E_ARG;
+  if (!rc_model_kind_ok(m, kinds) || !aligned) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!arrays || m->device != ctx->device) return RC_E_ARG;
   DeviceGuard g(ctx->device);
@@ -432,9 +351,6 @@ rc_status rc_ctx_create(int device, rc_ctx** out) {
   return RC_OK;
 }
 
-void rc_stream_release_(const rc_ctx* ctx);  // rc_stream.hip: the cached host pipeline
-void rc_resume_release_(const rc_ctx* ctx);  // rc_resume.hip: the stream API's staging
-
 rc_status rc_ctx_destroy(rc_ctx* ctx) {
   if (!ctx) return RC_E_ARG;
   DeviceGuard g(ctx->device);
@@ -445,33 +361,6 @@ rc_status rc_ctx_destroy(rc_ctx* ctx) {
   (void)hipFree(ctx->inv);
   (void)hipStreamDestroy(ctx->own);
   delete ctx;
-  return RC_OK;
-}
-
-// internal (not in the header): the context's device and current stream, for the other
-// translation units of the library
-rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device) {
-  if (!ctx || !s || !device) return RC_E_ARG;
-  *s = ctx->cur;
-  *device = ctx->device;
-  return RC_OK;
-}
-
-// internal: what the container writer needs to know about a model
-rc_status rc_model_describe_(const rc_model* m, int* kind, int* device, uint32_t* n_symbols,
-                             uint32_t* total, const uint32_t** c_host, uint32_t* increment,
-                             uint32_t* limit, uint32_t* period) {
-  // (a static model set or a wide model is neither: its callers, the container writer among
-  // them, take single-table one-byte models only)
-  if (!m || (m->kind != RC_KIND_STATIC && m->kind != RC_KIND_ADAPTIVE)) return RC_E_ARG;
-  *kind = m->kind;
-  *device = m->device;
-  *n_symbols = m->kind == 0 ? m->args.n : m->ap.n;
-  *total = m->args.total;
-  *c_host = m->c_host;
-  *increment = m->ap.inc;
-  *limit = m->ap.limit;
-  *period = m->period;
   return RC_OK;
 }
 
@@ -691,7 +580,7 @@ rc_status rc_encode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
                           const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
   // (a static model set is coded by the indexed calls only, a wide model by the wide calls only)
   return batch_call(
-      ctx, m, 1u << RC_KIND_STATIC | 1u << RC_KIND_ADAPTIVE, true, n_chunks,
+      ctx, m, RC_KINDS_SINGLE, true, n_chunks,
       syms && sym_off && out && out_off && out_len && flags,
       m && m->kind == RC_KIND_ADAPTIVE ? "adaptive encode launch" : "encode launch", [&] {
         if (m->kind == RC_KIND_ADAPTIVE)
@@ -708,7 +597,7 @@ rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
                           const uint64_t* code_off, const uint64_t* code_len, uint8_t* syms_out,
                           const uint64_t* sym_off, uint32_t n_chunks, uint32_t* flags) {
   return batch_call(
-      ctx, m, 1u << RC_KIND_STATIC | 1u << RC_KIND_ADAPTIVE, true, n_chunks,
+      ctx, m, RC_KINDS_SINGLE, true, n_chunks,
       code && code_off && code_len && syms_out && sym_off && flags,
       m && m->kind == RC_KIND_ADAPTIVE ? "adaptive decode launch" : "decode launch", [&] {
         if (m->kind == RC_KIND_ADAPTIVE)
@@ -759,11 +648,12 @@ rc_status rc_model_set_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* o
                             [&](SetPlan* p) { rc_set_plan(n_models, total_freq, p); });
 }
 
-// The device snapshot of a checked set for `plan` (rc_set_plan's, or rc_order1_plan's with maps: the period x 256 context-map bytes of an order-1 set, kept behind the tables)
+// The device snapshot of a checked set for `plan` (rc_set_plan's, or rc_order1_plan's with maps:
+// the period x 256 context-map bytes of an order-1 set, kept behind the tables, and its lag)
 static rc_status set_build(rc_ctx* ctx, int kind, uint32_t n_models, uint32_t n_symbols,
                            const uint32_t* c_freq, const uint32_t* cum_freq, uint32_t total_freq,
                            const SetPlan& plan, const uint8_t* maps, uint32_t period,
-                           uint32_t first_row, rc_model** out) {
+                           uint32_t lag, uint32_t first_row, rc_model** out) {
   if (!plan.enc_lanes || !plan.dec_lanes) return RC_E_BAD_MODEL;  // unreachable
   // cum rows, cum[0 .. 256] with the entries from n_symbols on holding the total (so a symbol
   // past the alphabet has c = 0 in the encoder's cum-only layout), and the rows' buckets
@@ -806,7 +696,7 @@ static rc_status set_build(rc_ctx* ctx, int kind, uint32_t n_models, uint32_t n_
     mm->o1.map = (const uint8_t*)(d + row_bytes + lut_bytes);
     mm->o1.first_row = first_row;
     mm->o1.period = period;
-    mm->o1_lag = 1;
+    mm->o1_lag = lag;
   }
   *out = mm;
   return RC_OK;
@@ -822,7 +712,7 @@ rc_status rc_model_create_static_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_
   SetPlan plan;
   rc_set_plan(n_models, total_freq, &plan);
   return set_build(ctx, RC_KIND_SET, n_models, n_symbols, c_freq, cum_freq, total_freq, plan,
-                   nullptr, 0, 0, out);
+                   nullptr, 0, 0, 0, out);
 }
 
 rc_status rc_encode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_t* syms,
@@ -853,156 +743,110 @@ rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_
 
 // ---- order-1 sets (rc_order1.h; kernels in rc_order1.hip) ----
 
-// what rc_model_create_order1_set accepts beyond the set's rules (include/range_coder.h)
+// One description of an order-1 set for the plain, periodic and lagged calls: (period, lag) is
+// (1, 1), (period, 1) or (period, lag).
+
+// What the constructors accept: a period and a lag of 1, 2, 4 or 8 (RC_E_ARG, before any table is
+// looked at), the set's rules, then a first_row and `period` map slices that name rows of the set
+// (the map's rules do not depend on the lag)
 static rc_status order1_check(u32 n_models, u32 n_symbols, const u32* c, const u32* cum,
-                              u32 total, const uint8_t* ctx_map, u32 first_row) {
-  if (!ctx_map) return RC_E_ARG;
+                              u32 total, u32 period, u32 lag, const uint8_t* ctx_map,
+                              u32 first_row) {
+  if (!ctx_map || !o1_period_ok(period) || !o1_lag_ok(lag)) return RC_E_ARG;
   const rc_status ok = set_check(n_models, n_symbols, c, cum, total);
   if (ok != RC_OK) return ok;
   if (first_row >= n_models) return RC_E_BAD_MODEL;
-  for (u32 s = 0; s < n_symbols; ++s)
-    if (ctx_map[s] >= n_models) return RC_E_BAD_MODEL;
+  for (u32 i = 0; i < period * n_symbols; ++i)
+    if (ctx_map[i] >= n_models) return RC_E_BAD_MODEL;
   return RC_OK;
 }
 
-// Internal test hooks (not in include/range_coder.h; host only, no device needed).
-// rc_model_order1_check_: rc_model_create_order1_set's validation of its tables and its map.
+// rc_model_set_plan_ for an order-1 set of `period` maps (the decoder's LDS includes them; at
+// period 1 the encoder's numbers are the set's).  The plan does not depend on the lag: a lagged
+// set stages what the periodic set of its (K, total, P) stages and keeps its contexts in registers.
+static rc_status order1_plan_hook(u32 n_models, u32 total, u32 period, u32 lag, uint32_t* out) {
+  if (!o1_period_ok(period) || !o1_lag_ok(lag)) return RC_E_ARG;
+  return plan_hook<SetPlan>(n_models >= 1 && n_models <= RC_MAX_SET_MODELS, total, out,
+                            [&](SetPlan* p) { rc_order1_plan(n_models, total, period, p); });
+}
+
+static rc_status order1_create(rc_ctx* ctx, u32 n_models, u32 n_symbols, const u32* c_freq,
+                               const u32* cum_freq, u32 total_freq, u32 period, u32 lag,
+                               const uint8_t* ctx_map, u32 first_row, rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !ctx_map || !out) return RC_E_ARG;
+  *out = nullptr;
+  // (a bad period or lag is the check's first refusal)
+  const rc_status ok = order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, period, lag,
+                                    ctx_map, first_row);
+  if (ok != RC_OK) return ok;
+  SetPlan plan;
+  rc_order1_plan(n_models, total_freq, period, &plan);
+  // the kernels stage 256 entries per slice: a symbol past the alphabet (a flagged chunk) maps to
+  // row 0
+  uint8_t maps[O1_MAX_PERIOD * 256] = {0};
+  for (u32 ph = 0; ph < period; ++ph)
+    memcpy(maps + 256 * ph, ctx_map + (size_t)ph * n_symbols, n_symbols);
+  return set_build(ctx, RC_KIND_ORDER1, n_models, n_symbols, c_freq, cum_freq, total_freq, plan,
+                   maps, period, lag, first_row, out);
+}
+
+// Internal test hooks (not in include/range_coder.h; host only, no device needed): the
+// constructors' validation and their plan, for rc_model_create_order1_set
+// (tests/test_order1_model.py), _periodic (tests/test_periodic_model.py) and _lagged
+// (tests/test_lag_model.py).
 rc_status rc_model_order1_check_(uint32_t n_models, uint32_t n_symbols, const uint32_t* c_freq,
                                  const uint32_t* cum_freq, uint32_t total_freq,
                                  const uint8_t* ctx_map, uint32_t first_row) {
-  return order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, ctx_map, first_row);
+  return order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, 1, 1, ctx_map, first_row);
 }
-// rc_model_order1_plan_: rc_model_set_plan_ for an order-1 set (the decoder's LDS includes the
-// map; the encoder's numbers are the set's).
+rc_status rc_model_order1_check_periodic_(uint32_t n_models, uint32_t n_symbols,
+                                          const uint32_t* c_freq, const uint32_t* cum_freq,
+                                          uint32_t total_freq, uint32_t period,
+                                          const uint8_t* ctx_map, uint32_t first_row) {
+  return order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, period, 1, ctx_map,
+                      first_row);
+}
+rc_status rc_model_order1_check_lagged_(uint32_t n_models, uint32_t n_symbols,
+                                        const uint32_t* c_freq, const uint32_t* cum_freq,
+                                        uint32_t total_freq, uint32_t period, uint32_t lag,
+                                        const uint8_t* ctx_map, uint32_t first_row) {
+  return order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, period, lag, ctx_map,
+                      first_row);
+}
 rc_status rc_model_order1_plan_(uint32_t n_models, uint32_t total_freq, uint32_t* out) {
-  return plan_hook<SetPlan>(n_models >= 1 && n_models <= RC_MAX_SET_MODELS, total_freq, out,
-                            [&](SetPlan* p) { rc_order1_plan(n_models, total_freq, 1, p); });
+  return order1_plan_hook(n_models, total_freq, 1, 1, out);
+}
+rc_status rc_model_order1_plan_periodic_(uint32_t n_models, uint32_t total_freq, uint32_t period,
+                                         uint32_t* out) {
+  return order1_plan_hook(n_models, total_freq, period, 1, out);
+}
+rc_status rc_model_order1_plan_lagged_(uint32_t n_models, uint32_t total_freq, uint32_t period,
+                                       uint32_t lag, uint32_t* out) {
+  return order1_plan_hook(n_models, total_freq, period, lag, out);
 }
 
 rc_status rc_model_create_order1_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
                                      const uint32_t* c_freq, const uint32_t* cum_freq,
                                      uint32_t total_freq, const uint8_t* ctx_map,
                                      uint32_t first_row, rc_model** out) {
-  if (!ctx || !c_freq || !cum_freq || !ctx_map || !out) return RC_E_ARG;
-  *out = nullptr;
-  const rc_status ok =
-      order1_check(n_models, n_symbols, c_freq, cum_freq, total_freq, ctx_map, first_row);
-  if (ok != RC_OK) return ok;
-  SetPlan plan;
-  rc_order1_plan(n_models, total_freq, 1, &plan);
-  // the kernels stage 256 entries: a symbol past the alphabet (a flagged chunk) maps to row 0
-  uint8_t map256[256] = {0};
-  memcpy(map256, ctx_map, n_symbols);
-  return set_build(ctx, RC_KIND_ORDER1, n_models, n_symbols, c_freq, cum_freq, total_freq, plan,
-                   map256, 1, first_row, out);
+  return order1_create(ctx, n_models, n_symbols, c_freq, cum_freq, total_freq, 1, 1, ctx_map,
+                       first_row, out);
 }
-
-// what rc_model_create_order1_set_periodic accepts: a period of 1, 2, 4 or 8 (RC_E_ARG), then
-// order1_check's rules over every slice of the map
-static rc_status order1_check_periodic(u32 n_models, u32 n_symbols, const u32* c, const u32* cum,
-                                       u32 total, u32 period, const uint8_t* ctx_map,
-                                       u32 first_row) {
-  if (!ctx_map || !o1_period_ok(period)) return RC_E_ARG;
-  for (u32 ph = 0; ph < period; ++ph) {
-    const rc_status ok = order1_check(n_models, n_symbols, c, cum, total,
-                                      ctx_map + (size_t)ph * n_symbols, first_row);
-    if (ok != RC_OK) return ok;
-  }
-  return RC_OK;
-}
-
-// rc_model_order1_check_periodic_ / rc_model_order1_plan_periodic_: the two hooks above with a
-// period (tests/test_periodic_model.py); at period 1 the plan is rc_model_order1_plan_'s.
-rc_status rc_model_order1_check_periodic_(uint32_t n_models, uint32_t n_symbols,
-                                          const uint32_t* c_freq, const uint32_t* cum_freq,
-                                          uint32_t total_freq, uint32_t period,
-                                          const uint8_t* ctx_map, uint32_t first_row) {
-  return order1_check_periodic(n_models, n_symbols, c_freq, cum_freq, total_freq, period, ctx_map,
-                               first_row);
-}
-rc_status rc_model_order1_plan_periodic_(uint32_t n_models, uint32_t total_freq, uint32_t period,
-                                         uint32_t* out) {
-  if (!o1_period_ok(period)) return RC_E_ARG;
-  return plan_hook<SetPlan>(
-      n_models >= 1 && n_models <= RC_MAX_SET_MODELS, total_freq, out,
-      [&](SetPlan* p) { rc_order1_plan(n_models, total_freq, period, p); });
-}
-
 rc_status rc_model_create_order1_set_periodic(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
                                               const uint32_t* c_freq, const uint32_t* cum_freq,
                                               uint32_t total_freq, uint32_t period,
                                               const uint8_t* ctx_map, uint32_t first_row,
                                               rc_model** out) {
-  if (!ctx || !c_freq || !cum_freq || !ctx_map || !out) return RC_E_ARG;
-  *out = nullptr;
-  if (!o1_period_ok(period)) return RC_E_ARG;
-  // (period 1: the old call itself, so the two cannot drift apart)
-  if (period == 1)
-    return rc_model_create_order1_set(ctx, n_models, n_symbols, c_freq, cum_freq, total_freq,
-                                      ctx_map, first_row, out);
-  const rc_status ok = order1_check_periodic(n_models, n_symbols, c_freq, cum_freq, total_freq,
-                                             period, ctx_map, first_row);
-  if (ok != RC_OK) return ok;
-  SetPlan plan;
-  rc_order1_plan(n_models, total_freq, period, &plan);
-  // the kernels stage 256 entries per slice: a symbol past the alphabet maps to row 0
-  uint8_t maps[O1_MAX_PERIOD * 256] = {0};
-  for (u32 ph = 0; ph < period; ++ph)
-    memcpy(maps + 256 * ph, ctx_map + (size_t)ph * n_symbols, n_symbols);
-  return set_build(ctx, RC_KIND_ORDER1, n_models, n_symbols, c_freq, cum_freq, total_freq, plan,
-                   maps, period, first_row, out);
+  return order1_create(ctx, n_models, n_symbols, c_freq, cum_freq, total_freq, period, 1, ctx_map,
+                       first_row, out);
 }
-
-// what rc_model_create_order1_set_lagged accepts: a period and a lag of 1, 2, 4 or 8 (RC_E_ARG),
-// then the periodic rules (the map's rules do not depend on the lag)
-static rc_status order1_check_lagged(u32 n_models, u32 n_symbols, const u32* c, const u32* cum,
-                                     u32 total, u32 period, u32 lag, const uint8_t* ctx_map,
-                                     u32 first_row) {
-  if (!ctx_map || !o1_period_ok(period) || !o1_lag_ok(lag)) return RC_E_ARG;
-  return order1_check_periodic(n_models, n_symbols, c, cum, total, period, ctx_map, first_row);
-}
-
-// rc_model_order1_check_lagged_ / rc_model_order1_plan_lagged_: the periodic hooks with a lag
-// (tests/test_lag_model.py).  The plan does not depend on the lag: a lagged set stages what the
-// periodic set of its (K, total, P) stages and keeps its contexts in registers.
-rc_status rc_model_order1_check_lagged_(uint32_t n_models, uint32_t n_symbols,
-                                        const uint32_t* c_freq, const uint32_t* cum_freq,
-                                        uint32_t total_freq, uint32_t period, uint32_t lag,
-                                        const uint8_t* ctx_map, uint32_t first_row) {
-  return order1_check_lagged(n_models, n_symbols, c_freq, cum_freq, total_freq, period, lag,
-                             ctx_map, first_row);
-}
-rc_status rc_model_order1_plan_lagged_(uint32_t n_models, uint32_t total_freq, uint32_t period,
-                                       uint32_t lag, uint32_t* out) {
-  if (!o1_lag_ok(lag)) return RC_E_ARG;
-  return rc_model_order1_plan_periodic_(n_models, total_freq, period, out);
-}
-
 rc_status rc_model_create_order1_set_lagged(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
                                             const uint32_t* c_freq, const uint32_t* cum_freq,
                                             uint32_t total_freq, uint32_t period, uint32_t lag,
                                             const uint8_t* ctx_map, uint32_t first_row,
                                             rc_model** out) {
-  if (!ctx || !c_freq || !cum_freq || !ctx_map || !out) return RC_E_ARG;
-  *out = nullptr;
-  if (!o1_period_ok(period) || !o1_lag_ok(lag)) return RC_E_ARG;
-  // (lag 1: the periodic call itself, so the two cannot drift apart)
-  if (lag == 1)
-    return rc_model_create_order1_set_periodic(ctx, n_models, n_symbols, c_freq, cum_freq,
-                                               total_freq, period, ctx_map, first_row, out);
-  const rc_status ok = order1_check_lagged(n_models, n_symbols, c_freq, cum_freq, total_freq,
-                                           period, lag, ctx_map, first_row);
-  if (ok != RC_OK) return ok;
-  SetPlan plan;
-  rc_order1_plan(n_models, total_freq, period, &plan);
-  // the kernels stage 256 entries per slice: a symbol past the alphabet maps to row 0
-  uint8_t maps[O1_MAX_PERIOD * 256] = {0};
-  for (u32 ph = 0; ph < period; ++ph)
-    memcpy(maps + 256 * ph, ctx_map + (size_t)ph * n_symbols, n_symbols);
-  const rc_status st = set_build(ctx, RC_KIND_ORDER1, n_models, n_symbols, c_freq, cum_freq,
-                                 total_freq, plan, maps, period, first_row, out);
-  if (st == RC_OK) (*out)->o1_lag = lag;
-  return st;
+  return order1_create(ctx, n_models, n_symbols, c_freq, cum_freq, total_freq, period, lag,
+                       ctx_map, first_row, out);
 }
 
 rc_status rc_encode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,

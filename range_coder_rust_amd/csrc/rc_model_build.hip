@@ -18,7 +18,7 @@
 //     k_ideal_bits_order1 prices a batch under an order-1 set (rc_order1.h);
 //   * the k_cj_* kernels are that clustering on the device, jointly over the (phase, context)
 //     items of periodic pair counts (rc_cluster_contexts_dev).
-#include "rc_common.h"
+#include "rc_host.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -842,26 +842,6 @@ __global__ __launch_bounds__(256) void k_cj_refresh(
 // ------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------
-struct rc_ctx;  // rc_kernels.hip
-hipError_t set_allow_lds(const void* kernel);  // rc_indexed.hip: a whole CU's LDS as dynamic LDS
-extern "C" {
-rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device);  // rc_kernels.hip
-}
-
-namespace {
-struct DevSet {
-  int prev = -1;
-  explicit DevSet(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DevSet() {
-    int now = -1;
-    if (prev >= 0 && hipGetDevice(&now) == hipSuccess && now != prev) (void)hipSetDevice(prev);
-  }
-};
-}  // namespace
-
 // rc_histogram_pairs (PER = false, period 1), rc_histogram_pairs_periodic (PER = true, period 1
 // included) and rc_histogram_pairs_lagged (one kernel per lag): each call keeps its own
 // instantiation of the kernel
@@ -869,13 +849,13 @@ template <class Kern>
 static rc_status histogram_pairs_launch(Kern kern, rc_ctx* ctx, u32 period, const uint8_t* syms,
                                         const uint64_t* sym_off, uint32_t n_chunks,
                                         uint64_t* pair_hist, uint64_t* first_hist) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (!ctx || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (period != 1 && period != 2 && period != 4 && period != 8) return RC_E_ARG;
   if (n_chunks == 0 || (!pair_hist && !first_hist)) return RC_OK;
   if (!syms || !sym_off) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -903,12 +883,12 @@ extern "C" {
 
 rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms, const uint64_t* sym_off,
                        uint32_t n_chunks, uint32_t* chunk_hist, uint64_t* hist) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (!ctx || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_chunks == 0 || (!chunk_hist && !hist)) return RC_OK;
   if (!syms || !sym_off) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -918,25 +898,25 @@ rc_status rc_histogram(rc_ctx* ctx, const uint8_t* syms, const uint64_t* sym_off
   // RC_HIST_HOT=0 (in the environment of rc_ctx_create) turns the ballot-counted hot symbol
   // off (measurements)
   hipLaunchKernelGGL(k_histogram, dim3(grid), dim3(256), 0, s, syms, sym_off, n_chunks,
-                     chunk_hist, hist, (u32)rc_ctx_knobs_(ctx).hist_hot);
+                     chunk_hist, hist, (u32)ctx->knobs.hist_hot);
   return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
 }
 
 rc_status rc_histogram_order1(rc_ctx* ctx, uint32_t n_models, const uint8_t* ctx_map_host,
                               uint32_t first_row, const uint8_t* syms, const uint64_t* sym_off,
                               uint32_t n_chunks, uint64_t* hist) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS || !ctx_map_host ||
-      n_models < 1 || n_models > RC_MAX_SET_MODELS || first_row >= n_models)
+  if (!ctx || n_chunks > RC_MAX_CHUNKS || !ctx_map_host || n_models < 1 ||
+      n_models > RC_MAX_SET_MODELS || first_row >= n_models)
     return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   O1HistMap map;
   for (u32 i = 0; i < 256; ++i)
     if (ctx_map_host[i] >= n_models) return RC_E_ARG;
   memcpy(map.w, ctx_map_host, 256);
   if (n_chunks == 0) return RC_OK;
   if (!syms || !sym_off || !hist) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -986,18 +966,18 @@ rc_status rc_histogram_pairs_lagged(rc_ctx* ctx, uint32_t period, uint32_t lag,
 
 rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* syms,
                                const uint64_t* sym_off, uint32_t n_chunks, double* bits) {
-  hipStream_t s;
-  int dev, mdev;
-  const u32* rows_dev;
-  const uint8_t* map_dev;
-  u32 first_row, K, n;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (!rc_model_order1_rows_(o1, &rows_dev, &map_dev, &first_row, &K, &n, &mdev))
-    return RC_E_ARG;  // kinds do not mix
-  if (mdev != dev) return RC_E_ARG;
+  if (!ctx || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
+  if (!rc_model_kind_ok(o1, 1u << RC_KIND_ORDER1)) return RC_E_ARG;  // kinds do not mix
+  if (o1->device != dev) return RC_E_ARG;
+  // the set's cum rows ([K][257]) and its staged map (`period` slices of 256), device memory
+  const u32* const rows_dev = o1->o1.s.rows;
+  const uint8_t* const map_dev = o1->o1.map;
+  const u32 first_row = o1->o1.first_row, K = o1->o1.s.k;
   if (n_chunks == 0) return RC_OK;
   if (!syms || !sym_off || !bits) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   // the set keeps its tables on the device only (K cum rows cum[0 .. 256], the entries from n on
   // holding the total): read them back, then PModel::ideal_code_length (pmodel.rs:14-40) per row
@@ -1024,8 +1004,8 @@ rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* s
   }
   double* d = nullptr;
   if (hipMallocAsync((void**)&d, icl_bytes, s) != hipSuccess) return RC_E_DEVICE;
-  const u32 period = rc_model_order1_period_(o1);  // (> 1: map_dev holds `period` slices)
-  const u32 lag = rc_model_order1_lag_(o1);  // (> 1: the kernel of that lag, whatever the period)
+  const u32 period = o1->o1.period;  // (> 1: map_dev holds `period` slices)
+  const u32 lag = o1->o1_lag;  // (> 1: the kernel of that lag, whatever the period)
   const auto kern = lag == 2   ? k_ideal_bits_order1_lag<2>
                     : lag == 4 ? k_ideal_bits_order1_lag<4>
                     : lag == 8 ? k_ideal_bits_order1_lag<8>
@@ -1057,14 +1037,14 @@ rc_status rc_ideal_bits_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t* s
 rc_status rc_histogram_wide(rc_ctx* ctx, const void* syms, const uint64_t* sym_off,
                             uint32_t n_chunks, uint32_t n_bins, uint32_t* chunk_hist,
                             uint64_t* hist, uint64_t* oob) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS || n_bins < 1 ||
-      n_bins > RC_MAX_WIDE_SYMBOLS || ((uintptr_t)syms & 1u) != 0)
+  if (!ctx || n_chunks > RC_MAX_CHUNKS || n_bins < 1 || n_bins > RC_MAX_WIDE_SYMBOLS ||
+      ((uintptr_t)syms & 1u) != 0)
     return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_chunks == 0 || (!chunk_hist && !hist && !oob)) return RC_OK;
   if (!syms || !sym_off) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -1091,16 +1071,16 @@ uint32_t rc_histogram_wide_copies_(uint32_t n_bins) {
 
 rc_status rc_ideal_bits_wide(rc_ctx* ctx, const rc_model* wide, const void* syms,
                              const uint64_t* sym_off, uint32_t n_chunks, double* bits) {
-  hipStream_t s;
-  int dev, mdev;
-  const u32* row_dev;
-  u32 n;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  if (!rc_model_wide_row_(wide, &row_dev, &n, &mdev)) return RC_E_ARG;  // kinds do not mix
+  if (!ctx || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
+  if (!rc_model_kind_ok(wide, 1u << RC_KIND_WIDE)) return RC_E_ARG;  // kinds do not mix
   if (((uintptr_t)syms & 1u) != 0) return RC_E_ARG;  // 16-bit symbols
   if (n_chunks == 0) return RC_OK;
-  if (!syms || !sym_off || !bits || mdev != dev) return RC_E_ARG;
-  DevSet g(dev);
+  if (!syms || !sym_off || !bits || wide->device != dev) return RC_E_ARG;
+  const u32* const row_dev = wide->wide.row;
+  const u32 n = wide->wide.m.n;
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   // the model keeps its table on the device only (the cum row cum[0 .. n], cum[n] = total): read
   // it back, then PModel::ideal_code_length (pmodel.rs:14-40) per symbol exactly as
@@ -1339,14 +1319,14 @@ rc_status rc_cluster_contexts_dev(rc_ctx* ctx, uint32_t period, const uint64_t* 
                                   uint32_t max_models, uint8_t* ctx_map_out,
                                   uint32_t* first_row_out, uint32_t* n_models_out,
                                   double* cost_bits_out) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK) return RC_E_ARG;
+  if (!ctx) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (period != 1 && period != 2 && period != 4 && period != 8) return RC_E_ARG;
   if (!pair_hist || !first_hist || !ctx_map_out || !first_row_out || !n_models_out ||
       max_models < 1 || max_models > RC_MAX_SET_MODELS || n_symbols < 1 || n_symbols > 256)
     return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   const u32 I = 256u * period + 1u;
   // one allocation: D, V, cost, rmin, tot, tot_hi (8-byte entries), then live, rarg, log, hdr
@@ -1446,11 +1426,11 @@ rc_status rc_cluster_contexts_dev(rc_ctx* ctx, uint32_t period, const uint64_t* 
 rc_status rc_ideal_bits(rc_ctx* ctx, const uint32_t* c_host, uint32_t n_symbols,
                         uint32_t total_freq, const uint32_t* chunk_hist, uint32_t n_chunks,
                         double* bits) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !c_host || n_symbols < 1 || n_symbols > 256 ||
-      total_freq < 1 || n_chunks > RC_MAX_CHUNKS)
+  if (!ctx || !c_host || n_symbols < 1 || n_symbols > 256 || total_freq < 1 ||
+      n_chunks > RC_MAX_CHUNKS)
     return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_chunks == 0) return RC_OK;
   if (!chunk_hist || !bits) return RC_E_ARG;
   // PModel::ideal_code_length (pmodel.rs:14-40): (ln total - ln c) / ln 2; symbols outside the
@@ -1459,7 +1439,7 @@ rc_status rc_ideal_bits(rc_ctx* ctx, const uint32_t* c_host, uint32_t n_symbols,
   const double lt = log((double)total_freq);
   for (u32 i = 0; i < 256; ++i)
     icl[i] = (i < n_symbols && c_host[i] > 0) ? (lt - log((double)c_host[i])) / M_LN2 : INFINITY;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   double* d = nullptr;
   if (hipMallocAsync((void**)&d, sizeof icl, s) != hipSuccess) return RC_E_DEVICE;
   void* pin = rc_pinned_scratch_(sizeof icl);

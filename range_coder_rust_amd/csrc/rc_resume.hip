@@ -17,7 +17,7 @@
 //   low + range overflows            -> RC_F_BAD_MODEL (upper_bound().unwrap(), :138-146)
 //   decoder needs a byte past the end -> RC_F_TRUNCATED (pop_front().unwrap(), decoder.rs:33)
 // u64 products wrap (release-build semantics of the reference).
-#include "rc_common.h"
+#include "rc_host.h"
 #include "rc_udiv.h"
 
 #include <stddef.h>
@@ -457,18 +457,6 @@ __global__ __launch_bounds__(RWG) void k_stream_service(SvcBox* box, u32 epoch, 
   if (lane == 0) sys_store(&box->alive, 2 * epoch + 2);
 }
 
-struct Dev {
-  int prev = -1;
-  explicit Dev(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~Dev() {
-    int now = -1;
-    if (prev >= 0 && hipGetDevice(&now) == hipSuccess && now != prev) (void)hipSetDevice(prev);
-  }
-};
-
 // The host variants' staging: one pinned host block and its device mirror per context, grown on
 // demand and kept until rc_ctx_destroy.  Every transfer is one DMA between the two (pageable
 // caller memory is only touched by host memcpy), so copies and the kernel are plainly ordered
@@ -557,7 +545,7 @@ struct SvcAtExit {
 
 // RC_STREAM_SERVICE=0 in the environment of rc_ctx_create sends every call of that context down
 // the launch path (RcKnobs, rc_common.h)
-bool svc_enabled(const rc_ctx* ctx) { return rc_ctx_knobs_(ctx).stream_service; }
+bool svc_enabled(const rc_ctx* ctx) { return ctx->knobs.stream_service; }
 
 // Test hook (tests/test_gpu_stream.py, not in include/range_coder.h): the wave's idle time in
 // 10-ns ticks for the waves launched from now on (0: SVC_IDLE_US), so a test can make waves
@@ -609,7 +597,7 @@ template <class Fill>
 bool svc_call(const rc_ctx* ctx, Svc* sv, int dev, Fill fill, rc_status* err) {
   if (sv->dead || sv->broken) return false;
   if (!sv->box) {
-    Dev g(dev);
+    DeviceGuard g(dev);
     void* hb = nullptr;
     if (hipHostMalloc(&hb, sizeof(SvcBox) + SVC_BLOCK,
                       hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
@@ -644,7 +632,7 @@ bool svc_call(const rc_ctx* ctx, Svc* sv, int dev, Fill fill, rc_status* err) {
     }
     // no wave of the current epoch running: start one (it takes the pending request)
     if (!sv->launched || __atomic_load_n(&b->alive, __ATOMIC_ACQUIRE) == 2 * sv->epoch + 2) {
-      Dev g(dev);
+      DeviceGuard g(dev);
       ++sv->epoch;
       hipLaunchKernelGGL(k_stream_service, dim3(1), dim3(RWG), 0, sv->stream, sv->dbox_host,
                          sv->epoch, idle_ticks(),
@@ -702,18 +690,16 @@ void rc_svc_yield_all_() {
 
 extern "C" {
 
-rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device);  // rc_kernels.hip
-
 rc_status rc_stream_encode(rc_ctx* ctx, rc_stream_state* states, const uint32_t* triples,
                            const uint64_t* sym_off, uint32_t n_streams, uint8_t* out,
                            const uint64_t* out_off, uint64_t* out_len, uint8_t* nbytes,
                            uint32_t finish, uint32_t* flags) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_streams > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (!ctx || n_streams > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_streams == 0) return RC_OK;
   if (!states || !triples || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
-  Dev g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   hipLaunchKernelGGL(k_stream_encode, dim3((n_streams + RWG - 1) / RWG), dim3(RWG), 0, s,
                      states, triples, sym_off, n_streams, out, out_off, out_len, nbytes, finish,
@@ -726,14 +712,14 @@ rc_status rc_stream_decode(rc_ctx* ctx, const uint32_t* c, const uint32_t* cum,
                            const uint8_t* code, const uint64_t* code_off,
                            const uint64_t* code_len, uint8_t* syms, const uint64_t* sym_off,
                            uint32_t n_streams, uint32_t* flags) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || n_streams > RC_MAX_CHUNKS) return RC_E_ARG;
+  if (!ctx || n_streams > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_symbols < 1 || n_symbols > 256) return RC_E_BAD_MODEL;
   if (n_streams == 0) return RC_OK;
   if (!c || !cum || !states || !code || !code_off || !code_len || !syms || !sym_off || !flags)
     return RC_E_ARG;
-  Dev g(dev);
+  DeviceGuard g(dev);
   rc_svc_yield_all_();
   hipLaunchKernelGGL(k_stream_decode, dim3((n_streams + RWG - 1) / RWG), dim3(RWG), 0, s, c,
                      cum, n_symbols, total_freq, states, code, code_off, code_len, syms, sym_off,
@@ -744,10 +730,9 @@ rc_status rc_stream_decode(rc_ctx* ctx, const uint32_t* c, const uint32_t* cum,
 rc_status rc_stream_encode_host(rc_ctx* ctx, rc_stream_state* state, const uint32_t* triples,
                                 uint64_t n, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
                                 uint8_t* nbytes, uint32_t finish, uint32_t* flags_out) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !state || !out_len || (n && !triples))
-    return RC_E_ARG;
+  if (!ctx || !state || !out_len || (n && !triples)) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   const u64 need = RC_STREAM_MAX_BYTES(n, finish);
   *out_len = 0;
   if (out_cap < need || (need && !out)) {
@@ -793,7 +778,7 @@ rc_status rc_stream_encode_host(rc_ctx* ctx, rc_stream_state* state, const uint3
       return fl ? RC_E_CHUNK : RC_OK;
     }
   }
-  Dev g(dev);  // (the service path makes no HIP call but its wave's launch, guarded there)
+  DeviceGuard g(dev);  // (the service path makes no HIP call but its wave's launch, guarded there)
   char* d = nullptr;
   std::shared_ptr<Stage> keep;
   std::unique_lock<std::mutex> lk;
@@ -849,11 +834,9 @@ rc_status rc_stream_decode_host(rc_ctx* ctx, const uint32_t* c, const uint32_t* 
                                 uint32_t n_symbols, uint32_t total_freq, rc_stream_state* state,
                                 const uint8_t* code, uint64_t code_len, uint8_t* syms,
                                 uint64_t n, uint32_t* flags_out) {
-  hipStream_t s;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s, &dev) != RC_OK || !state || !c || !cum || (n && !syms) ||
-      (code_len && !code))
-    return RC_E_ARG;
+  if (!ctx || !state || !c || !cum || (n && !syms) || (code_len && !code)) return RC_E_ARG;
+  const hipStream_t s = ctx->cur;
+  const int dev = ctx->device;
   if (n_symbols < 1 || n_symbols > 256) return RC_E_BAD_MODEL;
   // the window this call can read: Decoder::new's 8 bytes and <= 12 per symbol
   const u64 p0 = state->stage == 0 ? 0 : state->pos;
@@ -901,7 +884,7 @@ rc_status rc_stream_decode_host(rc_ctx* ctx, const uint32_t* c, const uint32_t* 
       return fl ? RC_E_CHUNK : RC_OK;
     }
   }
-  Dev g(dev);
+  DeviceGuard g(dev);
   char* d = nullptr;
   std::shared_ptr<Stage> keep;
   std::unique_lock<std::mutex> lk;

@@ -197,6 +197,8 @@ static __device__ __forceinline__ void rc_set_prio(const ModelArgs& m) {
 // workgroups of `kernel` the current device holds at once with `lds` bytes of dynamic LDS
 // (occupancy x CUs), cached per (device, kernel, lds); 0 when the runtime cannot say (host)
 u32 rc_resident_wgs(const void* kernel, int block, size_t lds);
+// lets `kernel` take a whole CU's LDS as dynamic LDS (rc_indexed.hip; once per device and kernel)
+hipError_t set_allow_lds(const void* kernel);
 
 // Small bucket models (k_decode_static LUT 4: 2048 < total <= 2^16; the pair decoder, LUT 3, is
 // opt-in, RC_DEC_PAIR).  LDS

@@ -27,7 +27,7 @@
 // whole time.  Each batch is staged in HBM at its host ranges' addresses mod 64, so the copy
 // kernel moves 16-B vectors on both sides whatever the caller's alignment.  RC_STREAM_DMA=1 (or
 // memory that cannot be mapped) moves outputs with hipMemcpyAsync too.
-#include "rc_common.h"
+#include "rc_host.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -52,25 +52,7 @@
                           // 46.7 GB/s each way with both directions at once; 2048 drops to 33)
 #endif
 
-struct rc_ctx;
-struct rc_model;
-extern "C" {
-rc_status rc_ctx_stream_(rc_ctx* ctx, hipStream_t* s, int* device);
-}
-
 namespace {
-
-struct DevSet {
-  int prev = -1;
-  explicit DevSet(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DevSet() {
-    int now = -1;
-    if (prev >= 0 && hipGetDevice(&now) == hipSuccess && now != prev) (void)hipSetDevice(prev);
-  }
-};
 
 // set on the worker threads of rc_*_multi, which page-locked the caller's whole buffers once:
 // a worker registering a sub-range again would, on unregistering it, unpin the whole range
@@ -387,19 +369,19 @@ extern "C" {
 rc_status rc_encode_host(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
                          const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
                          const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
-  hipStream_t s0;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s0, &dev) != RC_OK || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  // (model sets and wide models: their own device calls only)
-  if (rc_model_is_set_(m) || rc_model_is_wide_(m) || rc_model_is_order1_(m)) return RC_E_ARG;
+  if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s0 = ctx->cur;
+  const int dev = ctx->device;
+  // (every other kind of model: its own device calls only)
+  if (!rc_model_kind_ok(m, RC_KINDS_SINGLE)) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
     if (sym_off[k + 1] < sym_off[k] || out_off[k + 1] < out_off[k]) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   // a chunk the kernel flags RC_F_TOO_LONG (never read nor written) is staged as empty
   auto too_long = [&](u32 k) { return sym_off[k + 1] - sym_off[k] > RC_MAX_CHUNK_SYMBOLS; };
-  const RcKnobs& kn = rc_ctx_knobs_(ctx);
+  const RcKnobs& kn = ctx->knobs;
   std::vector<Batch> bs = plan(
       kn.stream_batch_bytes ? kn.stream_batch_bytes : (u64)RC_STREAM_BATCH_BYTES,
       n_chunks,
@@ -473,18 +455,18 @@ rc_status rc_encode_host(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
 rc_status rc_decode_host(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
                          const uint64_t* code_off, const uint64_t* code_len, uint8_t* syms_out,
                          const uint64_t* sym_off, uint32_t n_chunks, uint32_t* flags) {
-  hipStream_t s0;
-  int dev;
-  if (rc_ctx_stream_(ctx, &s0, &dev) != RC_OK || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
-  // (model sets and wide models: their own device calls only)
-  if (rc_model_is_set_(m) || rc_model_is_wide_(m) || rc_model_is_order1_(m)) return RC_E_ARG;
+  if (!ctx || !m || n_chunks > RC_MAX_CHUNKS) return RC_E_ARG;
+  const hipStream_t s0 = ctx->cur;
+  const int dev = ctx->device;
+  // (every other kind of model: its own device calls only)
+  if (!rc_model_kind_ok(m, RC_KINDS_SINGLE)) return RC_E_ARG;
   if (n_chunks == 0) return RC_OK;
   if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
     if (sym_off[k + 1] < sym_off[k]) return RC_E_ARG;
-  DevSet g(dev);
+  DeviceGuard g(dev);
   auto too_long = [&](u32 k) { return sym_off[k + 1] - sym_off[k] > RC_MAX_CHUNK_SYMBOLS; };
-  const RcKnobs& kn = rc_ctx_knobs_(ctx);
+  const RcKnobs& kn = ctx->knobs;
   std::vector<Batch> bs = plan(
       kn.stream_batch_bytes ? kn.stream_batch_bytes : (u64)RC_STREAM_BATCH_BYTES,
       n_chunks,
@@ -601,9 +583,7 @@ rc_status rc_encode_host_multi(rc_ctx* const* ctxs, const rc_model* const* model
   if (n_chunks == 0) return RC_OK;
   if (!syms || !sym_off || !out || !out_off || !out_len || !flags) return RC_E_ARG;
   for (u32 i = 0; i < n_ctx; ++i)
-    if (!ctxs[i] || !models[i] || rc_model_is_set_(models[i]) ||
-        rc_model_is_wide_(models[i]) || rc_model_is_order1_(models[i]))
-      return RC_E_ARG;
+    if (!ctxs[i] || !rc_model_kind_ok(models[i], RC_KINDS_SINGLE)) return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
     if (sym_off[k + 1] < sym_off[k] || out_off[k + 1] < out_off[k]) return RC_E_ARG;
   // pinned once for every device (each device's call then finds its range already pinned)
@@ -626,9 +606,7 @@ rc_status rc_decode_host_multi(rc_ctx* const* ctxs, const rc_model* const* model
   if (n_chunks == 0) return RC_OK;
   if (!code || !code_off || !code_len || !syms_out || !sym_off || !flags) return RC_E_ARG;
   for (u32 i = 0; i < n_ctx; ++i)
-    if (!ctxs[i] || !models[i] || rc_model_is_set_(models[i]) ||
-        rc_model_is_wide_(models[i]) || rc_model_is_order1_(models[i]))
-      return RC_E_ARG;
+    if (!ctxs[i] || !rc_model_kind_ok(models[i], RC_KINDS_SINGLE)) return RC_E_ARG;
   for (u32 k = 0; k < n_chunks; ++k)
     if (sym_off[k + 1] < sym_off[k]) return RC_E_ARG;
   u64 cmin = ~0ull, cmax = 0;

@@ -210,14 +210,15 @@ def histogram_pairs(syms, sym_off, pair_hist=None, first_hist=None, ctx=None):
 
 def histogram_pairs_periodic(syms, sym_off, period, pair_hist=None, first_hist=None, ctx=None,
                              lag=1):
-    """rc_histogram_pairs_periodic on torch tensors (async, torch's current stream).
+    """rc_histogram_pairs_lagged on torch tensors (async, torch's current stream); at lag 1 that
+    is rc_histogram_pairs_periodic.
 
     Returns (pair_hist, first_hist): int64[period, 256, 256], [ph][p][s] = the positions i >= 1
     of a chunk with i % period == ph, sym[i-1] = p and sym[i] = s (i counted from the chunk's
     start), and int64[256] as histogram_pairs gives it.  Chunk boundaries reset the context.
     Given arrays are added into.  period: 1, 2, 4 or 8.
 
-    lag (1, 2, 4 or 8; rc_histogram_pairs_lagged for lag > 1): the pairs are taken at that
+    lag (1, 2, 4 or 8): the pairs are taken at that
     distance, [ph][p][s] = the positions i >= lag with sym[i-lag] = p, and first_hist counts the
     positions i < lag of every chunk, so that the two sum to the number of symbols."""
     torch = _torch()
@@ -242,15 +243,9 @@ def histogram_pairs_periodic(syms, sym_off, period, pair_hist=None, first_hist=N
     if first_hist is None:
         first_hist = torch.zeros(256, dtype=torch.int64, device=syms.device)
     ctx.bind_stream()
-    if lag != 1:
-        N.check(ctx._lib.rc_histogram_pairs_lagged(ctx.handle, period, lag, _ptr(syms),
-                                                   _ptr(sym_off), n, _ptr(pair_hist),
-                                                   _ptr(first_hist)),
-                "rc_histogram_pairs_lagged")
-        return pair_hist, first_hist
-    N.check(ctx._lib.rc_histogram_pairs_periodic(ctx.handle, period, _ptr(syms), _ptr(sym_off),
-                                                 n, _ptr(pair_hist), _ptr(first_hist)),
-            "rc_histogram_pairs_periodic")
+    N.check(ctx._lib.rc_histogram_pairs_lagged(ctx.handle, period, lag, _ptr(syms), _ptr(sym_off),
+                                               n, _ptr(pair_hist), _ptr(first_hist)),
+            "rc_histogram_pairs_lagged")
     return pair_hist, first_hist
 
 
