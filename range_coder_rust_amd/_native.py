@@ -159,6 +159,13 @@ def load():
     if hasattr(L, "rc_symof_table_"):
         L.rc_symof_table_.argtypes = [_U32, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U32)]
         L.rc_symof_table_.restype = _I
+    # host-only hooks of the single-table static models: the class of a table (9 words) and the
+    # wide bucket decoder's table (tests/test_static_cases.py; an earlier revision has neither)
+    if hasattr(L, "rc_model_static_plan_"):
+        L.rc_model_static_plan_.argtypes = [_U32, _P, _P, _U32, _P]
+        L.rc_model_static_plan_.restype = _I
+        L.rc_bucket_table_.argtypes = [_U32, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U32)]
+        L.rc_bucket_table_.restype = _I
     L.rc_model_create_static_wide.argtypes = [_P, _U32, _P, _P, _U32, ctypes.POINTER(_P)]
     L.rc_encode_batch_wide.argtypes = [_P, _P, _P, _P, _U32, _P, _P, _P, _P]
     L.rc_decode_batch_wide.argtypes = [_P, _P, _P, _P, _P, _P, _P, _U32, _P]

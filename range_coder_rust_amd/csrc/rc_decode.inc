@@ -934,7 +934,7 @@ size_t rc_static_decode_lds(const ModelArgs& a, int lut, u32 wgs) {
   // the q-to-symbol bytes, the 16-B entries, the rings (at most 143,360 B: rc_static.h)
   if (lut == 6) return (size_t)a.symof_mask + 1 + 256 * 16 + rings;
   const bool dl = a.direct != 0, dl2 = a.direct == 2;
-  const bool sm = a.total >= 256 && a.total <= 65536;
+  const bool sm = rc_static_sm(a.total);
   const bool smb = sm && !dl;  // LUT 4: 8-B buckets and the 16-B symbol table
   const bool rows = DEC_ROWS && dl2 && !a.flat;  // (direct == 2 implies sm)
   const size_t lut_n = a.flat ? 0 : ((size_t)a.lut_max + 1) * (dl2 ? 4 : smb ? 2 : 1);  // (smb: 16-B table)

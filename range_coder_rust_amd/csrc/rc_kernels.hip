@@ -117,6 +117,9 @@ void* rc_pinned_scratch_(size_t bytes) {
   return t_pinned.p;
 }
 
+// the division a model of `total` is coded with (its kernels' DIV)
+static int div_of(u32 total) { return (total & (total - 1)) == 0 ? DIV_POW2 : DIV_MAGIC; }
+
 // range_par_total's constants for `total` (DIV_POW2's shift, DIV_MAGIC's reciprocal and the
 // small models' f64 1/total rounded up)
 static void div_constants(ModelArgs& a, u32 total) {
@@ -225,7 +228,7 @@ static rc_status model_upload(rc_ctx* ctx, int kind, u32 total, std::initializer
   memset(mm, 0, sizeof *mm);
   mm->kind = kind;
   mm->device = ctx->device;
-  mm->div = (total & (total - 1)) == 0 ? DIV_POW2 : DIV_MAGIC;
+  mm->div = div_of(total);
   mm->dmem = d;
   *out = mm;
   *base = (char*)d;
@@ -382,29 +385,35 @@ rc_status rc_ctx_synchronize(rc_ctx* ctx) {
   return hipStreamSynchronize(ctx->cur) == hipSuccess ? RC_OK : RC_E_DEVICE;
 }
 
-rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t* c_freq,
-                                 const uint32_t* cum_freq, uint32_t total_freq, rc_model** out) {
-  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
-  *out = nullptr;
+// Everything rc_model_create_static works out on the host for a table: the class of the model
+// (a.direct, a.flat, the bucket geometry, which tables it carries), the constants
+// of its total and the four segments of its device snapshot.  a's table pointers stay null: they
+// are set once the segments are uploaded.  rc_model_static_plan_ and rc_bucket_table_ report from
+// the same function, so a test sees the class a model really gets.
+struct StaticTables {
+  ModelArgs a;
+  std::vector<uint2> tab;      // [256] (cum, c)
+  std::vector<u32> lut;        // the class's decoder table (buckets or direct entries)
+  std::vector<u32> pair;       // pair buckets, or empty
+  std::vector<uint8_t> symof;  // q-to-symbol bytes, or empty
+  bool complete;               // 256 symbols, every c_freq > 0
+};
+static rc_status static_tables(u32 n_symbols, const u32* c_freq, const u32* cum_freq,
+                               u32 total_freq, StaticTables* st) {
   if (n_symbols < 1 || n_symbols > 256 || total_freq < 1) return RC_E_BAD_MODEL;
-  u64 acc = 0;
-  for (u32 i = 0; i < n_symbols; ++i) {
-    if ((u64)cum_freq[i] != acc) return RC_E_BAD_MODEL;
-    acc += c_freq[i];
-  }
-  if (acc != (u64)total_freq) return RC_E_BAD_MODEL;
+  if (!table_ok(n_symbols, c_freq, cum_freq, total_freq)) return RC_E_BAD_MODEL;
 
-  std::vector<uint2> tab(256);
+  std::vector<uint2>& tab = st->tab;
+  tab.resize(256);
   for (u32 i = 0; i < 256; ++i)
     tab[i] = i < n_symbols ? make_uint2(cum_freq[i], c_freq[i]) : make_uint2(0xFFFFFFFFu, 0u);
 
-  ModelArgs a;
+  ModelArgs& a = st->a;
   memset(&a, 0, sizeof a);
   a.n = n_symbols;
   a.total = total_freq;
   a.ftotal = (float)total_freq;
   div_constants(a, total_freq);
-  const bool pow2 = (total_freq & (total_freq - 1)) == 0;
   // bucket table of 2^bits buckets: s0 = symbol containing the bucket's first frequency, s1 =
   // the next symbol with c > 0 starting inside the bucket, split = its offset (0xFFFF: none);
   // padded to a power of two (the kernel masks the bucket index) with the last bucket, so
@@ -414,7 +423,8 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
     return bucket_table(n_symbols, c_freq, cum_freq, total_freq, bits, shift_out);
   };
   a.lut_bits = total_freq <= 65536 ? SM_LUT_BITS : LUT_BITS;
-  std::vector<u32> lut = bucket_lut(a.lut_bits, &a.lut_shift);
+  std::vector<u32>& lut = st->lut;
+  lut = bucket_lut(a.lut_bits, &a.lut_shift);
   a.lut_max = (u32)lut.size() - 1;
   if (total_freq > 2048 && lut.size() != (1u << a.lut_bits)) return RC_E_BAD_MODEL;  // unreachable
 
@@ -452,7 +462,8 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
   // frequencies, and every c < 2^16 (16-bit fields).  Per bucket both candidates of its bucket
   // entry: s0 (holding the bucket's first frequency) and s1 (the next symbol with c > 0 that
   // starts inside the bucket; none: s1 = s0, so the choice between them does not matter).
-  std::vector<u32> pair;
+  std::vector<u32>& pair = st->pair;
+  pair.clear();
   u32 cmax = 0;
   for (u32 i = 0; i < n_symbols; ++i) cmax = std::max(cmax, c_freq[i]);
   if (!a.direct && total_freq > 32768 && total_freq <= 65536 && cmax < 65536) {
@@ -506,31 +517,52 @@ rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t
     lut.swap(l8);
   }
   // the same class through the direct q-to-symbol table (the decoder's LUT 6)
-  std::vector<uint8_t> symof;
+  std::vector<uint8_t>& symof = st->symof;
+  symof.clear();
   if (!a.direct && total_freq <= 65536) {
     symof = symof_table(n_symbols, c_freq, cum_freq, total_freq);
     a.symof_mask = (u32)symof.size() - 1;
   }
+  st->complete = n_symbols == 256;
+  for (u32 i = 0; i < n_symbols; ++i) st->complete = st->complete && c_freq[i] > 0;
+  return RC_OK;
+}
+
+// The encoder variant of a static model (k_encode_static's SM): 0 outside the small-model range,
+// there 1 for an alphabet with a symbol the coder can reject and 2 for a complete one.  (The flat
+// model runs variant 3 whatever this says: rc_static_encode_launch reads a.flat.)
+static int static_smv(const ModelArgs& a, bool complete) {
+  return rc_static_sm(a.total) ? (complete ? 2 : 1) : 0;
+}
+
+rc_status rc_model_create_static(rc_ctx* ctx, uint32_t n_symbols, const uint32_t* c_freq,
+                                 const uint32_t* cum_freq, uint32_t total_freq, rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
+  *out = nullptr;
+  StaticTables st;
+  const rc_status built = static_tables(n_symbols, c_freq, cum_freq, total_freq, &st);
+  if (built != RC_OK) return built;
+  ModelArgs& a = st.a;
   const size_t tab_bytes = 256 * sizeof(uint2);
-  const size_t lut_bytes = lut.size() * sizeof(u32);
-  const size_t pair_bytes = pair.size() * sizeof(u32);
+  const size_t lut_bytes = st.lut.size() * sizeof(u32);
+  const size_t pair_bytes = st.pair.size() * sizeof(u32);
   rc_model* mm = nullptr;
   char* d = nullptr;
   const rc_status up = model_upload(
       ctx, RC_KIND_STATIC, total_freq,
-      {{tab.data(), tab_bytes}, {lut.data(), lut_bytes}, {pair.data(), pair_bytes},
-       {symof.data(), symof.size()}},
+      {{st.tab.data(), tab_bytes}, {st.lut.data(), lut_bytes}, {st.pair.data(), pair_bytes},
+       {st.symof.data(), st.symof.size()}},
       &mm, &d);
   if (up != RC_OK) return up;
   a.tab = (const uint2*)d;
   a.lut = (const u32*)(d + tab_bytes);
   a.pair = pair_bytes ? (const u32*)(d + tab_bytes + lut_bytes) : nullptr;
   // (every segment before it is a multiple of 16 B long: the kernel copies the table as words)
-  a.symof = symof.empty() ? nullptr : (const uint8_t*)(d + tab_bytes + lut_bytes + pair_bytes);
+  a.symof = st.symof.empty() ? nullptr
+                             : (const uint8_t*)(d + tab_bytes + lut_bytes + pair_bytes);
   mm->args = a;
   for (u32 i = 0; i < n_symbols; ++i) mm->c_host[i] = c_freq[i];
-  mm->complete = n_symbols == 256;
-  for (u32 i = 0; i < n_symbols; ++i) mm->complete = mm->complete && c_freq[i] > 0;
+  mm->complete = st.complete;
   *out = mm;
   return RC_OK;
 }
@@ -586,8 +618,7 @@ rc_status rc_encode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* syms,
         if (m->kind == RC_KIND_ADAPTIVE)
           return rc_adaptive_encode_launch(ctx->cur, m->ap, syms, sym_off, n_chunks, out, out_off,
                                            out_len, flags);
-        const bool sm = m->args.total >= 256 && m->args.total <= 65536;
-        const int smv = sm ? (m->complete ? 2 : 1) : 0;
+        const int smv = static_smv(m->args, m->complete);
         return rc_static_encode_launch(ctx->cur, ctx->knobs, m->args, m->div, smv, syms, sym_off,
                                        n_chunks, out, out_off, out_len, flags);
       });
@@ -603,7 +634,7 @@ rc_status rc_decode_batch(rc_ctx* ctx, const rc_model* m, const uint8_t* code,
         if (m->kind == RC_KIND_ADAPTIVE)
           return rc_adaptive_decode_launch(ctx->cur, m->ap, code, code_off, code_len, syms_out,
                                            sym_off, n_chunks, flags);
-        const bool sm = m->args.total >= 256 && m->args.total <= 65536;
+        const bool sm = rc_static_sm(m->args.total);
         return m->div == DIV_POW2
                    ? rc_static_decode_launch_pow2(ctx->cur, ctx->knobs, m->args, sm, code,
                                                   code_off, code_len, syms_out, sym_off, n_chunks,
@@ -627,6 +658,41 @@ rc_status rc_symof_table_(uint32_t n_symbols, const uint32_t* c_freq, const uint
   *size = (u32)t.size();
   if (t.size() > cap) return RC_E_ARG;
   memcpy(out, t.data(), t.size());
+  return RC_OK;
+}
+
+// Internal test hook (host only): the class rc_model_create_static sorts a table into, as the
+// launchers read it.  out[9] = {sm (the kernels' SM variants), direct (0 buckets,
+// 1 4-byte direct entries, 2 16-byte direct entries), flat, has_pair, has_symof, lut_bits,
+// lut_shift, div (0 DIV_POW2, 1 DIV_MAGIC), the encoder variant rc_encode_batch launches (0
+// wide, 1 small and incomplete, 2 small and complete, 3 flat)}.
+rc_status rc_model_static_plan_(uint32_t n_symbols, const uint32_t* c_freq,
+                                const uint32_t* cum_freq, uint32_t total_freq, uint32_t* out) {
+  if (!c_freq || !cum_freq || !out) return RC_E_ARG;
+  StaticTables st;
+  const rc_status built = static_tables(n_symbols, c_freq, cum_freq, total_freq, &st);
+  if (built != RC_OK) return built;
+  const ModelArgs& a = st.a;
+  const u32 v[9] = {(u32)rc_static_sm(a.total), a.direct, a.flat, (u32)!st.pair.empty(),
+                    (u32)!st.symof.empty(), a.lut_bits, a.lut_shift, (u32)div_of(a.total),
+                    a.flat ? 3u : (u32)static_smv(a, st.complete)};
+  memcpy(out, v, sizeof v);
+  return RC_OK;
+}
+
+// Internal test hook (host only): the bucket words s0 | s1 << 8 | split << 16 that the wide
+// bucket decoder (k_decode_static LUT 0) gets for a model of total > 2^16, into out[0 .. cap);
+// *size: their number (2^LUT_BITS).
+rc_status rc_bucket_table_(uint32_t n_symbols, const uint32_t* c_freq, const uint32_t* cum_freq,
+                           uint32_t total_freq, uint32_t* out, uint32_t cap, uint32_t* size) {
+  if (!c_freq || !cum_freq || !out || !size) return RC_E_ARG;
+  StaticTables st;
+  const rc_status built = static_tables(n_symbols, c_freq, cum_freq, total_freq, &st);
+  if (built != RC_OK) return built;
+  if (rc_static_sm(st.a.total) || st.a.direct) return RC_E_BAD_MODEL;
+  *size = (u32)st.lut.size();
+  if (st.lut.size() > cap) return RC_E_ARG;
+  memcpy(out, st.lut.data(), st.lut.size() * sizeof(u32));
   return RC_OK;
 }
 

@@ -77,6 +77,10 @@
 
 enum { DIV_POW2 = 0, DIV_MAGIC = 1 };
 
+// The small-model range of total_freq: the kernels' SM variants (f32 / f64 range arithmetic,
+// ring checks of 3 bytes per symbol) code these totals, the wide variants every other one.
+static inline bool rc_static_sm(u32 total) { return total >= 256 && total <= 65536; }
+
 struct ModelArgs {
   const uint2* tab;  // [256] (cum, c); entries s >= n_symbols hold (0xFFFFFFFF, 0)
   const u32* lut;    // decoder buckets: s0 | s1 << 8 | split << 16 (small models, total <=

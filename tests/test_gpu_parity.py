@@ -70,8 +70,10 @@ def test_fixtures_gpu(ctx):
 
 def _random_model(rng, kind):
     n = int(rng.choice([1, 2, 3, 7, 10, 64, 200, 255, 256]))
-    if kind == "pow2":
-        bits = int(rng.integers(max(1, int(np.ceil(np.log2(n)))), 17))
+    if kind in ("pow2", "pow2big"):
+        # ("pow2big": the power-of-two totals above 2^16, the wide coders with a shift divisor)
+        bits = int(rng.integers(17, 32)) if kind == "pow2big" else \
+            int(rng.integers(max(1, int(np.ceil(np.log2(n)))), 17))
         total = 1 << bits
         w = rng.pareto(1.1, n) + 0.05
         c = np.maximum(1, np.floor(w / w.sum() * total)).astype(np.int64)
@@ -84,7 +86,7 @@ def _random_model(rng, kind):
     else:
         c = rng.integers(1, 300, n)
     c = c.astype(np.int64)
-    if n > 2 and kind != "pow2":
+    if n > 2 and kind not in ("pow2", "pow2big"):
         z = rng.random(n) < 0.15
         z[int(np.argmax(c))] = False
         c[z] = 0
@@ -92,9 +94,10 @@ def _random_model(rng, kind):
 
 
 @pytest.mark.parametrize("seed", range(8))
-@pytest.mark.parametrize("kind", ["pow2", "small", "big"])
+@pytest.mark.parametrize("kind", ["pow2", "small", "big", "pow2big"])
 def test_random_models_vs_oracle(ctx, seed, kind):
-    rng = np.random.default_rng(1000 * seed + {"pow2": 1, "small": 2, "big": 3}[kind])
+    rng = np.random.default_rng(1000 * seed + {"pow2": 1, "small": 2, "big": 3,
+                                               "pow2big": 4}[kind])
     c = _random_model(rng, kind)
     cum = cum_of(c)
     total = int(c.astype(np.uint64).sum())
