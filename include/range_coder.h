@@ -451,6 +451,38 @@ rc_status rc_stream_decode(rc_ctx* ctx, const uint32_t* c_dev, const uint32_t* c
                            const uint8_t* code_dev, const uint64_t* code_off_dev,
                            const uint64_t* code_len_dev, uint8_t* syms_dev,
                            const uint64_t* sym_off_dev, uint32_t n_streams, uint32_t* flags_dev);
+/* The same pair against a table per symbol, out of rows held in device memory: tables that both
+ * sides know beforehand and that change from symbol to symbol (chosen by side information, by
+ * position, by a model evaluated earlier), any number of rows, in one launch.
+ * A row table: n_rows tables of n_symbols (1..256) entries each, row-major in device memory:
+ * c_dev, cum_dev  n_rows * n_symbols uint32;  total_dev  n_rows uint32.
+ * Evaluated as given, like rc_stream_decode's table: no consistency requirement.
+ * row_of_dev: one uint32 per symbol, indexed like syms (stream k's symbols are
+ * [sym_off[k], sym_off[k+1])): the row that symbol is coded against.
+ * Symbol i of stream k, g = sym_off[k] + i, r = row_of[g], is coded exactly as rc_stream_decode
+ * would with the table (c + r n_symbols, cum + r n_symbols, n_symbols, total[r]), or
+ * rc_stream_encode with the triple (c[r][s], cum[r][s], total[r]), s = syms[g]: the same state
+ * (Decoder::new on a fresh one), finish, nbytes and capacity rule, sticky flags, and stop before
+ * the first failing symbol.  Two checks come first, per symbol: row_of[g] >= n_rows is
+ * RC_F_BAD_MODEL; encode only, syms[g] >= n_symbols is RC_F_BAD_SYMBOL (sticky, too).
+ * RC_E_BAD_MODEL: n_symbols outside 1..256; RC_E_ARG: a null pointer (nbytes_dev may be NULL), or
+ * n_rows == 0 with n_streams > 0.
+ * The decoder runs one wave per stream and reads code bytes in aligned dwords, never outside the
+ * 64-B segments that hold a byte of the stream; it reads no table entry outside the rows.     */
+rc_status rc_stream_decode_rows(rc_ctx* ctx, const uint32_t* c_dev, const uint32_t* cum_dev,
+                                const uint32_t* total_dev, uint32_t n_rows, uint32_t n_symbols,
+                                const uint32_t* row_of_dev, rc_stream_state* states_dev,
+                                const uint8_t* code_dev, const uint64_t* code_off_dev,
+                                const uint64_t* code_len_dev, uint8_t* syms_dev,
+                                const uint64_t* sym_off_dev, uint32_t n_streams,
+                                uint32_t* flags_dev);
+rc_status rc_stream_encode_rows(rc_ctx* ctx, const uint32_t* c_dev, const uint32_t* cum_dev,
+                                const uint32_t* total_dev, uint32_t n_rows, uint32_t n_symbols,
+                                const uint32_t* row_of_dev, const uint8_t* syms_dev,
+                                rc_stream_state* states_dev, const uint64_t* sym_off_dev,
+                                uint32_t n_streams, uint8_t* out_dev, const uint64_t* out_off_dev,
+                                uint64_t* out_len_dev, uint8_t* nbytes_dev, uint32_t finish,
+                                uint32_t* flags_dev);
 /* One stream in host memory, synchronous (the host mirrors' Encoder / Decoder).  Only the bytes a
  * call can touch cross PCIe: the encoder's new bytes, the decoder's window
  * [pos, pos + RC_STREAM_MAX_BYTES(n, 0) + 8).  Return RC_E_CHUNK when a flag is set (in

@@ -13,6 +13,8 @@ from .api import (  # noqa: F401
     decode_chunks_wide,
     Order1ModelSet, encode_batch_order1, decode_batch_order1, encode_chunks_order1,
     decode_chunks_order1,
+    RowTable, stream_decode_rows_batch, stream_encode_rows_batch, encode_chunks_rows,
+    decode_chunks_rows,
 )
 from . import synth  # noqa: F401
 from .model_build import build_model, histogram, ideal_bits, quantize_counts, quantize_counts_wide  # noqa: F401

@@ -35,6 +35,7 @@ EXPORTS = (
     "rc_decode_host", "rc_synth_fill", "rc_histogram", "rc_quantize_counts", "rc_ideal_bits",
     "rc_container_pack", "rc_container_info_parse", "rc_container_offsets",
     "rc_stream_encode", "rc_stream_decode", "rc_stream_encode_host", "rc_stream_decode_host",
+    "rc_stream_decode_rows", "rc_stream_encode_rows",
     "rc_encode_host_multi", "rc_decode_host_multi",
     "rc_model_create_static_set", "rc_encode_batch_indexed", "rc_decode_batch_indexed",
     "rc_model_create_static_wide", "rc_encode_batch_wide", "rc_decode_batch_wide",
@@ -140,6 +141,10 @@ def load():
     SP = ctypes.POINTER(StreamState)
     L.rc_stream_encode.argtypes = [_P, _P, _P, _P, _U32, _P, _P, _P, _P, _U32, _P]
     L.rc_stream_decode.argtypes = [_P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _U32, _P]
+    L.rc_stream_decode_rows.argtypes = [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _P, _P, _P,
+                                        _U32, _P]
+    L.rc_stream_encode_rows.argtypes = [_P, _P, _P, _P, _U32, _U32, _P, _P, _P, _P, _U32, _P, _P,
+                                        _P, _P, _U32, _P]
     L.rc_stream_encode_host.argtypes = [_P, SP, _P, _U64, _P, _U64, ctypes.POINTER(_U64), _P,
                                         _U32, ctypes.POINTER(_U32)]
     L.rc_stream_decode_host.argtypes = [_P, _P, _P, _U32, _U32, SP, _P, _U64, _P, _U64,

@@ -41,6 +41,8 @@ __all__ = [
     "decode_chunks_indexed",
     "Order1ModelSet", "encode_batch_order1", "decode_batch_order1", "encode_chunks_order1",
     "decode_chunks_order1",
+    "RowTable", "stream_decode_rows_batch", "stream_encode_rows_batch", "encode_chunks_rows",
+    "decode_chunks_rows",
 ]
 
 
@@ -1486,6 +1488,198 @@ def stream_decode_batch(ctx, c, cum, total, states, code, code_off, code_len, sy
                                    _ptr(sym_off), n, _ptr(flags))
     N.check(rc, "rc_stream_decode")
     return flags[:n]
+
+
+def _check_rows(c, cum, total, row_of):
+    """The tensor checks of a row table and its per-symbol row indexes; returns (n_rows,
+    n_symbols)."""
+    torch = _torch()
+    for name, t in (("c", c), ("cum", cum), ("total", total), ("row_of", row_of)):
+        _check_dev(t, name, (torch.int32, torch.uint32))
+    if c.dim() != 2 or cum.shape != c.shape:
+        raise ValueError("c and cum must be 2-D (n_rows, n_symbols) tensors of one shape")
+    if total.numel() != c.shape[0]:
+        raise ValueError("total must have one entry per row")
+    return int(c.shape[0]), int(c.shape[1])
+
+
+def stream_decode_rows_batch(ctx, c, cum, total, row_of, states, code, code_off, code_len, syms,
+                             sym_off, flags=None):
+    """rc_stream_decode_rows on torch tensors: c, cum (n_rows, n_symbols) and total (n_rows)
+    uint32/int32 device tensors, row_of one uint32/int32 row index per symbol, indexed like syms;
+    the rest as stream_decode_batch.  Returns flags."""
+    torch = _torch()
+    n = states.shape[0]
+    n_rows, n_symbols = _check_rows(c, cum, total, row_of)
+    _check_dev(states, "states", (torch.int64,))
+    _check_dev(code, "code", (torch.uint8,))
+    _check_dev(syms, "syms", (torch.uint8,))
+    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
+        _check_dev(t, name, (torch.int64, torch.uint64))
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=states.device)
+    ctx.bind_stream()
+    rc = ctx._lib.rc_stream_decode_rows(ctx.handle, _ptr(c), _ptr(cum), _ptr(total), n_rows,
+                                        n_symbols, _ptr(row_of), _ptr(states), _ptr(code),
+                                        _ptr(code_off), _ptr(code_len), _ptr(syms), _ptr(sym_off),
+                                        n, _ptr(flags))
+    N.check(rc, "rc_stream_decode_rows")
+    return flags[:n]
+
+
+def stream_encode_rows_batch(ctx, c, cum, total, row_of, syms, states, sym_off, out, out_off,
+                             out_len=None, nbytes=None, finish=False, flags=None):
+    """rc_stream_encode_rows on torch tensors: the row table and row_of as in
+    stream_decode_rows_batch, syms uint8 (one per symbol, indexed by sym_off); the rest as
+    stream_encode_batch.  Returns (out_len, flags)."""
+    torch = _torch()
+    n = states.shape[0]
+    n_rows, n_symbols = _check_rows(c, cum, total, row_of)
+    _check_dev(states, "states", (torch.int64,))
+    _check_dev(syms, "syms", (torch.uint8,))
+    _check_dev(out, "out", (torch.uint8,))
+    for name, t in (("sym_off", sym_off), ("out_off", out_off)):
+        _check_dev(t, name, (torch.int64, torch.uint64))
+        if t.numel() != n + 1:
+            raise ValueError(f"{name} must have n_streams + 1 entries")
+    if nbytes is not None:
+        _check_dev(nbytes, "nbytes", (torch.uint8,))
+    if out_len is None:
+        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=states.device)
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=states.device)
+    ctx.bind_stream()
+    rc = ctx._lib.rc_stream_encode_rows(ctx.handle, _ptr(c), _ptr(cum), _ptr(total), n_rows,
+                                        n_symbols, _ptr(row_of), _ptr(syms), _ptr(states),
+                                        _ptr(sym_off), n, _ptr(out), _ptr(out_off), _ptr(out_len),
+                                        _ptr(nbytes), 1 if finish else 0, _ptr(flags))
+    N.check(rc, "rc_stream_encode_rows")
+    return out_len[:n], flags[:n]
+
+
+def _u32_rows(a, name, dim):
+    """a (tensor or array of non-negative integers below 2^32) as a contiguous uint32 numpy array"""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.ndim != dim:
+        raise ValueError(f"{name} must be {dim}-D")
+    if a.dtype == np.int32:
+        a = a.view(np.uint32)
+    elif a.dtype != np.uint32:
+        if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+            raise BadModelError(f"{name}: entry outside 0..2^32 - 1")
+        a = a.astype(np.uint32)
+    return np.ascontiguousarray(a)
+
+
+class RowTable:
+    """n_rows tables of n_symbols (1..256) entries each, held in device memory, for the calls
+    that code every symbol against a row of its own (rc_stream_decode_rows /
+    rc_stream_encode_rows).  c, cum: (n_rows, n_symbols); total: (n_rows).  The tables are used
+    as given (no consistency requirement, as with Decoder.decode's PModel)."""
+
+    def __init__(self, c, cum, total, ctx=None):
+        torch = _torch()
+        self.ctx = ctx or default_context()
+        c, cum, total = _u32_rows(c, "c", 2), _u32_rows(cum, "cum", 2), _u32_rows(total, "total", 1)
+        if cum.shape != c.shape or total.shape[0] != c.shape[0]:
+            raise ValueError("c and cum must have one shape, total one entry per row")
+        if c.shape[0] < 1 or not 1 <= c.shape[1] <= 256:
+            raise BadModelError("a row table has at least one row of 1..256 symbols")
+        self.n_rows, self.n_symbols = int(c.shape[0]), int(c.shape[1])
+        dev = torch.device("cuda", self.ctx.device)
+        self.c, self.cum, self.total = (torch.from_numpy(a.view(np.int32)).to(dev)
+                                        for a in (c, cum, total))
+
+    @classmethod
+    def from_counts(cls, counts, ctx=None):
+        """Rows from symbol counts: cum by FreqTable.calc_cum's rule (sample_impl.rs:61-69), total
+        the row's sum, which must fit 32 bits."""
+        return cls(*cls.tables_from_counts(counts), ctx=ctx)
+
+    @staticmethod
+    def tables_from_counts(counts):
+        """from_counts' (c, cum, total) as uint32 numpy arrays (host only)."""
+        c = np.asarray(counts)
+        if c.ndim != 2:
+            raise ValueError("counts must be 2-D (n_rows, n_symbols)")
+        if c.size and (c.min() < 0 or c.max() > 0xFFFFFFFF):
+            raise BadModelError("counts: entry outside 0..2^32 - 1")
+        c = c.astype(np.uint64)
+        run = np.cumsum(c, axis=1, dtype=np.uint64)
+        total = run[:, -1] if c.shape[1] else np.zeros(c.shape[0], np.uint64)
+        if total.size and total.max() > 0xFFFFFFFF:
+            raise BadModelError("counts: a row's total exceeds 2^32 - 1")
+        cum = np.zeros_like(run)
+        cum[:, 1:] = run[:, :-1]
+        return c.astype(np.uint32), cum.astype(np.uint32), total.astype(np.uint32)
+
+
+def _row_arrays(rows, lens):
+    rows = [np.ascontiguousarray(_u32_rows(r, "rows", 1)) for r in rows]
+    if [len(r) for r in rows] != list(lens):
+        raise ValueError("rows must give one row index per symbol of every chunk")
+    return rows
+
+
+def encode_chunks_rows(table, chunks, rows, raise_on_error=True):
+    """Encode a list of symbol sequences (bytes / uint8 arrays), symbol i of chunk k against row
+    rows[k][i] of `table` (a RowTable): fresh streams, finished.  Returns a list of bytes."""
+    torch = _torch()
+    arrs = [_u8_chunk(c) for c in chunks]
+    n = len(arrs)
+    if n == 0:
+        return []
+    dev = torch.device("cuda", table.ctx.device)
+    lens = np.array([len(a) for a in arrs], dtype=np.int64)
+    rows = _row_arrays(rows, lens)
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum(lens)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    out_off[1:] = np.cumsum([N.stream_max_bytes(L, True) for L in lens])
+    out_d = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
+    row_d = _to_dev([r.view(np.int32) for r in rows], sym_off[-1], dev)
+    states = stream_states(n, dev)
+    out_len, flags = stream_encode_rows_batch(
+        table.ctx, table.c, table.cum, table.total, row_d, _to_dev(arrs, sym_off[-1], dev),
+        states, torch.from_numpy(sym_off).to(dev), out_d, torch.from_numpy(out_off).to(dev),
+        finish=True)
+    fl, ol, host = flags.cpu().numpy(), out_len.cpu().numpy(), out_d.cpu().numpy()
+    if raise_on_error:
+        _raise_flagged(fl)
+    return [bytes(host[out_off[k]: out_off[k] + ol[k]]) for k in range(n)]
+
+
+def decode_chunks_rows(table, codes, rows, raise_on_error=True):
+    """Decode a list of code streams, len(rows[k]) symbols each, symbol i of stream k against row
+    rows[k][i] of `table`.  Returns a list of uint8 numpy arrays (a flagged stream's symbols
+    before its error, when raise_on_error is false)."""
+    torch = _torch()
+    n = len(codes)
+    if n == 0:
+        return []
+    dev = torch.device("cuda", table.ctx.device)
+    codes = [bytes(c) for c in codes]
+    rows = _row_arrays(rows, [len(r) for r in rows])
+    clen = np.array([len(c) for c in codes], dtype=np.int64)
+    coff = np.zeros(n, dtype=np.int64)
+    coff[1:] = np.cumsum(clen)[:-1]
+    sym_off = np.zeros(n + 1, dtype=np.int64)
+    sym_off[1:] = np.cumsum([len(r) for r in rows])
+    code_d = torch.from_numpy(np.frombuffer(b"".join(codes) + b"\0", dtype=np.uint8).copy()).to(dev)
+    syms_d = torch.zeros(max(int(sym_off[-1]), 1), dtype=torch.uint8, device=dev)
+    states = stream_states(n, dev)
+    flags = stream_decode_rows_batch(
+        table.ctx, table.c, table.cum, table.total,
+        _to_dev([r.view(np.int32) for r in rows], sym_off[-1], dev), states, code_d,
+        torch.from_numpy(coff).to(dev), torch.from_numpy(clen).to(dev), syms_d,
+        torch.from_numpy(sym_off).to(dev))
+    fl, host = flags.cpu().numpy(), syms_d.cpu().numpy()
+    got = states.cpu().numpy().view(np.uint64)[:, 4]
+    if raise_on_error:
+        _raise_flagged(fl)
+    return [host[sym_off[k]: sym_off[k] + int(got[k])].copy() for k in range(n)]
 
 
 # ----------------------------------------------------------------------------- host streaming
