@@ -467,8 +467,12 @@ rc_status rc_stream_decode(rc_ctx* ctx, const uint32_t* c_dev, const uint32_t* c
  * RC_F_BAD_MODEL; encode only, syms[g] >= n_symbols is RC_F_BAD_SYMBOL (sticky, too).
  * RC_E_BAD_MODEL: n_symbols outside 1..256; RC_E_ARG: a null pointer (nbytes_dev may be NULL), or
  * n_rows == 0 with n_streams > 0.
- * The decoder runs one wave per stream and reads code bytes in aligned dwords, never outside the
- * 64-B segments that hold a byte of the stream; it reads no table entry outside the rows.     */
+ * The decoder is one of two kernels with the same results, picked per launch by the stream count
+ * against the device's CU count: one wave per stream (fewer than 16 streams per CU, and always
+ * for 64 streams or fewer), which reads a symbol's whole row coalesced and code bytes in aligned
+ * dwords; or one lane per stream, which reads only the row entries its search visits and code
+ * bytes in aligned 8-byte words.  Neither reads a code byte outside the 64-B segments that hold a
+ * byte of the stream, or a table entry outside the rows.                                        */
 rc_status rc_stream_decode_rows(rc_ctx* ctx, const uint32_t* c_dev, const uint32_t* cum_dev,
                                 const uint32_t* total_dev, uint32_t n_rows, uint32_t n_symbols,
                                 const uint32_t* row_of_dev, rc_stream_state* states_dev,

@@ -171,6 +171,14 @@ def load():
         L.rc_model_static_plan_.restype = _I
         L.rc_bucket_table_.argtypes = [_U32, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U32)]
         L.rc_bucket_table_.restype = _I
+    # host-only hooks of rc_stream_decode_rows: the rule that picks its kernel, and a context's
+    # choice (0 the rule, 1 wave per stream, 2 lane per stream; tests/test_rows_plan.py,
+    # tools/kbench_rows.py; an earlier revision has neither)
+    if hasattr(L, "rc_rows_decode_plan_"):
+        L.rc_rows_decode_plan_.argtypes = [_U32, _U32, _U32]
+        L.rc_rows_decode_plan_.restype = _I
+        L.rc_rows_decoder_.argtypes = [_P, _U32]
+        L.rc_rows_decoder_.restype = _I
     L.rc_model_create_static_wide.argtypes = [_P, _U32, _P, _P, _U32, ctypes.POINTER(_P)]
     L.rc_encode_batch_wide.argtypes = [_P, _P, _P, _P, _U32, _P, _P, _P, _P]
     L.rc_decode_batch_wide.argtypes = [_P, _P, _P, _P, _P, _P, _P, _U32, _P]

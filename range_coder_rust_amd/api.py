@@ -1507,7 +1507,11 @@ def stream_decode_rows_batch(ctx, c, cum, total, row_of, states, code, code_off,
                              sym_off, flags=None):
     """rc_stream_decode_rows on torch tensors: c, cum (n_rows, n_symbols) and total (n_rows)
     uint32/int32 device tensors, row_of one uint32/int32 row index per symbol, indexed like syms;
-    the rest as stream_decode_batch.  Returns flags."""
+    the rest as stream_decode_batch.  Returns flags.
+
+    The library picks one of two kernels with the same results, by the stream count against the
+    device's CU count: one wave per stream (fewer than 16 streams per CU: a symbol's whole row
+    read coalesced), or one lane per stream (only the row entries the search visits)."""
     torch = _torch()
     n = states.shape[0]
     n_rows, n_symbols = _check_rows(c, cum, total, row_of)
@@ -1654,7 +1658,8 @@ def encode_chunks_rows(table, chunks, rows, raise_on_error=True):
 def decode_chunks_rows(table, codes, rows, raise_on_error=True):
     """Decode a list of code streams, len(rows[k]) symbols each, symbol i of stream k against row
     rows[k][i] of `table`.  Returns a list of uint8 numpy arrays (a flagged stream's symbols
-    before its error, when raise_on_error is false)."""
+    before its error, when raise_on_error is false).  One launch: a wave per stream for a short
+    list, a lane per stream from 16 streams per CU on (stream_decode_rows_batch)."""
     torch = _torch()
     n = len(codes)
     if n == 0:

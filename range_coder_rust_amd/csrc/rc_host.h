@@ -16,6 +16,10 @@ struct rc_ctx {
   hipStream_t cur;
   uint8_t* inv;  // 64 KiB device scratch for rc_synth_fill's inverse CDF
   RcKnobs knobs;  // read from the environment once, by rc_ctx_create (rc_common.h)
+  // rc_rows.hip only: rc_stream_decode_rows's decoder (rc_rows_decoder_: 0 by the rule, 1 wave,
+  // 2 lane) and the device's CU count for the rule (0: not asked yet)
+  u32 rows_decoder = 0;
+  u32 n_cus = 0;
 };
 
 enum {

@@ -16,6 +16,9 @@
 // RC_ROWS_D).  Code bytes are read as a wave-wide window of two 256-B halves, the second loaded
 // while the first is consumed; decoded symbols are collected per 64 and stored coalesced.
 //
+// Decode, many streams (k_stream_decode_rows_lane): one lane per stream, the
+// row walked in device memory by the lane itself; rows_decode_plan picks between the two.
+//
 // Encode: one lane per stream, rc_resume.hip's encoder body with the triple gathered from the
 // rows.  The arithmetic of both is the reference's, branch for branch (see rc_resume.hip).
 //
@@ -287,6 +290,186 @@ __global__ __launch_bounds__(RWG) void k_stream_decode_rows(
   }
 }
 
+// A lane's code bytes (k_stream_decode_rows_lane): the aligned 8 bytes at address wa, of which
+// `off` are consumed, and the 8 behind them, requested when the window moved on.  A window is
+// loaded only if it holds a byte of the stream ([lo8, lo8 + span8), the stream's own aligned
+// 8-byte windows: all inside the 64-B segments that hold a byte of the stream); any other reads
+// as 0 and is never consumed (the caller checks pos + nb <= code_len first).
+struct LaneWin {
+  u64 wa, cur, nxt;
+  u32 off;
+};
+static __device__ __forceinline__ u64 lwin_load(u64 a, u64 lo8, u64 span8) {
+  return a - lo8 < span8 ? gload64((const u64*)a) : 0ull;
+}
+static __device__ __forceinline__ void lwin_fill(LaneWin& w, u64 a, u64 lo8, u64 span8) {
+  w.wa = a & ~7ull;
+  w.off = (u32)a & 7u;
+  w.cur = lwin_load(w.wa, lo8, span8);
+  w.nxt = lwin_load(w.wa + 8, lo8, span8);
+}
+static __device__ __forceinline__ u32 lwin_byte(LaneWin& w, u64 lo8, u64 span8) {
+  if (w.off == 8) {
+    w.wa += 8;
+    w.cur = w.nxt;
+    w.nxt = lwin_load(w.wa + 8, lo8, span8);
+    w.off = 0;
+  }
+  const u32 half = w.off < 4 ? (u32)w.cur : (u32)(w.cur >> 32);
+  return (half >> (8 * (w.off++ & 3))) & 255u;
+}
+
+#ifndef RC_ROWS_LANE_L2
+#define RC_ROWS_LANE_L2 0  // 1: the search resolves two levels per round trip (scratch builds)
+#endif
+
+// FreqTable::find_index's bisection over row cr (sample_impl.rs:33-44), every comparison read
+// from the row in device memory: one dependent load per step.  With -DRC_ROWS_LANE_L2=1 a node's
+// two possible children are requested with the node (each only if the bisection can reach it from
+// here, which also keeps it inside the row): the same comparisons on the same path in half the
+// round trips, and measured slower (three loads and their address arithmetic
+// per round cost a lone wave more issue slots than the round trips they save).
+static __device__ __forceinline__ u32 lane_find_index(const u32* __restrict__ cr, u32 n_alpha,
+                                                      u64 rfreq) {
+  u32 left = 0, right = n_alpha - 1;
+#if RC_ROWS_LANE_L2
+  while (left < right) {
+    const u32 mid = (left + right) >> 1;
+    const bool has_r = mid + 1 < right, has_l = left < mid;
+    const u32 mid_r = (mid + 1 + right) >> 1, mid_l = (left + mid) >> 1;
+    const u32 v = gload(cr + mid + 1);  // (mid + 1 <= right < n_alpha)
+    const u32 vr = has_r ? gload(cr + mid_r + 1) : 0u;  // (mid_r + 1 <= right)
+    const u32 vl = has_l ? gload(cr + mid_l + 1) : 0u;  // (mid_l + 1 <= mid)
+    if ((u64)v <= rfreq) {
+      left = mid + 1;
+      if (has_r) {
+        if ((u64)vr <= rfreq) left = mid_r + 1;
+        else right = mid_r;
+      }
+    } else {
+      right = mid;
+      if (has_l) {
+        if ((u64)vl <= rfreq) left = mid_l + 1;
+        else right = mid_l;
+      }
+    }
+  }
+#else
+  while (left < right) {
+    const u32 mid = (left + right) >> 1;
+    if ((u64)gload(cr + mid + 1) <= rfreq) left = mid + 1;
+    else right = mid;
+  }
+#endif
+  return left;
+}
+
+// Decoder::decode x n, one lane per stream: k_stream_decode_rows's results for
+// launches of many streams, where 64 lanes doing one stream's scalar work leave the device idle.
+// Every lane walks its own row in device memory; the row index of symbol i + 2 and the total of
+// symbol i + 1 are requested while symbol i is coded.  A lane whose stream is done or flagged
+// touches no memory but its one write-back while the wave's longest stream runs on.
+__global__ __launch_bounds__(RWG) void k_stream_decode_rows_lane(
+    const u32* __restrict__ c_tab, const u32* __restrict__ cum_tab,
+    const u32* __restrict__ total_tab, u32 n_rows, u32 n_alpha, const u32* __restrict__ row_of,
+    rc_stream_state* __restrict__ st, const uint8_t* __restrict__ code,
+    const u64* __restrict__ code_off, const u64* __restrict__ code_len,
+    uint8_t* __restrict__ syms, const u64* __restrict__ sym_off, u32 n_streams,
+    u32* __restrict__ flags) {
+  const u32 k = blockIdx.x * RWG + threadIdx.x;
+  if (k >= n_streams) return;
+  RC_VGPR_FLOOR_80();
+  rc_stream_state S = st[k];
+  if (S.flags) {  // the reference panicked at an earlier call
+    flags[k] = S.flags;
+    return;
+  }
+  const u64 a0 = (u64)(code + gload64(code_off + k));  // address of the stream's byte 0
+  const u64 clen = gload64(code_len + k);
+  const u64 s0 = gload64(sym_off + k), n = gload64(sym_off + k + 1) - s0;
+  if (S.stage == 0 && clen < 8) {  // Decoder::new on fewer than 8 bytes (decoder.rs:14-23)
+    st[k].flags = RC_F_TRUNCATED;
+    flags[k] = RC_F_TRUNCATED;
+    return;
+  }
+  const u64 lo8 = a0 & ~7ull;
+  const u64 span8 = clen ? ((a0 + clen + 7) & ~7ull) - lo8 : 0;
+  // the rows of the first two symbols and the total of the first, before anything waits
+  const u32* const rp = row_of + s0;
+  u32 row_a = n > 0 ? gload(rp) : 0xFFFFFFFFu;
+  u32 row_b = n > 1 ? gload(rp + 1) : 0xFFFFFFFFu;
+  bool ok_a = row_a < n_rows;
+  u32 total_a = ok_a ? gload(total_tab + row_a) : 0u;
+  u64 low = S.lower_bound, range = S.range, data = S.data, pos = S.pos, done = S.n;
+  u32 sflags = 0;
+  LaneWin W;
+  if (S.stage == 0) {  // Decoder::new: the first 8 bytes
+    lwin_fill(W, a0, lo8, span8);
+    data = 0;
+    for (pos = 0; pos < 8; ++pos) data = (data << 8) | lwin_byte(W, lo8, span8);
+    S.stage = 1;
+  } else {
+    lwin_fill(W, a0 + pos, lo8, span8);
+  }
+  uint8_t* const op = syms + s0;
+  for (u64 i = 0; i < n; ++i) {
+    const u32 row_c = i + 2 < n ? gload(rp + i + 2) : 0xFFFFFFFFu;
+    const bool ok_b = row_b < n_rows;  // (no symbol i + 1: 2^32 - 1 names no row)
+    const u32 total_b = ok_b ? gload(total_tab + row_b) : 0u;
+    // a row index >= n_rows; then find_index's range_par_total dividing by zero
+    if (!ok_a || total_a == 0) {
+      sflags = RC_F_BAD_MODEL;
+      break;
+    }
+    // FreqTable::find_index (sample_impl.rs:27-45)
+    const u64 r = rc_udiv64(range, total_a);
+    const u64 rfreq = r ? rc_udiv64(data - low, r) : 0;
+    const u64 e = (u64)row_a * n_alpha;
+    const u32 left = lane_find_index(cum_tab + e, n_alpha, rfreq);
+    const Narrow q = narrow_r(low, range, r, gload(c_tab + e + left), gload(cum_tab + e + left),
+                              RC_F_CORRUPT);
+    if (q.err) {
+      sflags = q.err;
+      break;
+    }
+    u64 nl = q.low, nr = q.range;
+    u32 nb = 0;
+    while (((nl ^ (nl + nr)) >> 56) == 0) {  // no_carry_expansion (:110-116)
+      nl <<= 8;
+      nr <<= 8;
+      ++nb;
+    }
+    while (nr < TOP16) {  // range_reduction_expansion (:126-135)
+      nr = ~nl & (TOP16 - 1);
+      nl <<= 8;
+      nr <<= 8;
+      ++nb;
+    }
+    if (pos + nb > clen) {  // shift_left_buffer pops past the end (decoder.rs:31-35)
+      sflags = RC_F_TRUNCATED;
+      break;
+    }
+    low = nl;
+    range = nr;
+    pos += nb;
+    for (u32 j = 0; j < nb; ++j) data = (data << 8) | lwin_byte(W, lo8, span8);
+    gstore8(op + i, left);
+    ++done;
+    row_a = row_b;
+    ok_a = ok_b;
+    total_a = total_b;
+    row_b = row_c;
+  }
+  S.lower_bound = low;
+  S.range = range;
+  S.data = data;
+  S.pos = pos;
+  S.n = done;
+  S.flags = sflags;
+  st[k] = S;
+  flags[k] = sflags;
+}
+
 // Encoder::encode x n (+ finish) for stream k: rc_resume.hip's stream_encode_one with the triple
 // gathered from the rows
 __global__ __launch_bounds__(RWG) void k_stream_encode_rows(
@@ -379,9 +562,36 @@ __global__ __launch_bounds__(RWG) void k_stream_encode_rows(
   flags[k] = S.flags;
 }
 
+// Which decoder a launch takes: 0 the wave-per-stream kernel, 1 the lane-per-stream kernel
+// (the sweep).  The wave kernel's rate stops growing once every SIMD holds a few
+// of its waves; the lane kernel's grows with the stream count until the device is full of
+// lanes.  The two curves cross at kRowsLaneStreamsPerCu streams per CU in both alphabets
+// measured, so the rule does not look at n_symbols.  64 streams or fewer are one wave of the lane
+// kernel: always the wave kernel.  Monotone in n_streams.
+constexpr u32 kRowsLaneStreamsPerCu = 16;
+int rows_decode_plan(u32 n_streams, u32 n_symbols, u32 n_cus) {
+  (void)n_symbols;
+  if (n_streams <= 64) return 0;
+  return (u64)n_streams >= (u64)kRowsLaneStreamsPerCu * (n_cus ? n_cus : 1u) ? 1 : 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// Host-only hooks (tests/test_rows_plan.py, tools/kbench_rows.py; not in include/range_coder.h).
+// The rule above, callable without a device.
+int rc_rows_decode_plan_(uint32_t n_streams, uint32_t n_symbols, uint32_t n_cus) {
+  return rows_decode_plan(n_streams, n_symbols, n_cus);
+}
+
+// rc_stream_decode_rows of this context: 0 by the rule, 1 always the wave kernel, 2 always the
+// lane kernel.  Nothing else reads the value.
+rc_status rc_rows_decoder_(rc_ctx* ctx, uint32_t which) {
+  if (!ctx || which > 2) return RC_E_ARG;
+  ctx->rows_decoder = which;
+  return RC_OK;
+}
 
 rc_status rc_stream_decode_rows(rc_ctx* ctx, const uint32_t* c, const uint32_t* cum,
                                 const uint32_t* total, uint32_t n_rows, uint32_t n_symbols,
@@ -399,6 +609,23 @@ rc_status rc_stream_decode_rows(rc_ctx* ctx, const uint32_t* c, const uint32_t* 
     return RC_E_ARG;
   DeviceGuard g(dev);
   rc_svc_yield_all_();
+  bool lane = ctx->rows_decoder == 2;
+  if (ctx->rows_decoder == 0 && n_streams > 64) {  // the rule (the device's CU count, asked once)
+    if (!ctx->n_cus) {
+      int cus = 0;
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          cus < 1)
+        return RC_E_DEVICE;
+      ctx->n_cus = (u32)cus;
+    }
+    lane = rows_decode_plan(n_streams, n_symbols, ctx->n_cus) == 1;
+  }
+  if (lane) {
+    hipLaunchKernelGGL(k_stream_decode_rows_lane, dim3((n_streams + RWG - 1) / RWG), dim3(RWG), 0,
+                       s, c, cum, total, n_rows, n_symbols, row_of, states, code, code_off,
+                       code_len, syms, sym_off, n_streams, flags);
+    return hipGetLastError() == hipSuccess ? RC_OK : RC_E_DEVICE;
+  }
   auto kern = n_symbols <= 64 ? k_stream_decode_rows<1>
               : n_symbols <= 128 ? k_stream_decode_rows<2> : k_stream_decode_rows<4>;
   hipLaunchKernelGGL(kern, dim3(n_streams), dim3(RWG), 0, s, c, cum, total, n_rows, n_symbols,
