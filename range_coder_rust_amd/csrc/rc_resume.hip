@@ -9,16 +9,9 @@
 // 64-bit stream position) in rc_stream_state between launches, and take per-symbol triples
 // (encode) or the table of the next n symbols (decode).  One lane per stream: the host mirrors
 // (api.py Encoder / Decoder, range_coder.hpp) run one stream, so this path is latency-, not
-// bandwidth-bound; the arithmetic is the reference's, branch for branch, with its panics and
-// endless loops turned into sticky flags:
-//   total == 0                       -> RC_F_BAD_MODEL (u64 / 0, range_coder.rs:38-40)
-//   low + r*cum overflows            -> RC_F_BAD_MODEL (LowerBoundOverflow, :68-81)
-//   range == r*c == 0                -> RC_F_ZERO_FREQ / RC_F_CORRUPT (:83-85 never ends)
-//   low + range overflows            -> RC_F_BAD_MODEL (upper_bound().unwrap(), :138-146)
-//   decoder needs a byte past the end -> RC_F_TRUNCATED (pop_front().unwrap(), decoder.rs:33)
-// u64 products wrap (release-build semantics of the reference).
-#include "rc_host.h"
-#include "rc_udiv.h"
+// bandwidth-bound.  The arithmetic is the reference's, branch for branch; the coder step, its
+// sticky flags and the encoder body are rc_stream_dev.h's, shared with rc_rows.hip.
+#include "rc_stream_dev.h"
 
 #include <stddef.h>
 #include <string.h>
@@ -30,133 +23,23 @@
 #include <mutex>
 #include <unordered_map>
 
-#define RWG 64
-#define TOP8 (1ull << 56)  // range_coder.rs:23
-
 static_assert(sizeof(rc_stream_state) == 48, "rc_stream_state layout");
 
 namespace {
 
-// RangeCoder::param_update up to the renormalisation loops: the narrowed interval, or a flag
-struct Narrow {
-  u64 low, range;
-  u32 err;
-};
-
-// (r = range_par_total, range_coder.rs:38-40)
-static __device__ __forceinline__ Narrow narrow_r(u64 low, u64 range, u64 r, u32 c, u32 cum,
-                                                  u32 zero_flag) {
-  Narrow o{low, range, 0u};
-  const u64 nr = r * (u64)c;     // range_coder.rs:65
-  const u64 add = r * (u64)cum;  // :68
-  const u64 nl = low + add;
-  if (nl < add) o.err = RC_F_BAD_MODEL;          // overflowing_add -> Err (:68-81)
-  else if (nr == 0) o.err = zero_flag;           // no_carry_expansion never terminates
-  else if (nl + nr < nr) o.err = RC_F_BAD_MODEL;  // upper_bound() overflow (:138-146)
-  o.low = nl;
-  o.range = nr;
-  return o;
-}
-static __device__ __forceinline__ Narrow narrow(u64 low, u64 range, u32 c, u32 cum, u32 total,
-                                                u32 zero_flag) {
-  if (total == 0) return Narrow{low, range, RC_F_BAD_MODEL};  // range_par_total divides by 0
-  return narrow_r(low, range, rc_udiv64(range, total), c, cum, zero_flag);
-}
-
-// bytes the two renormalisation loops settle from (low, range), without applying them
-static __device__ __forceinline__ u32 settle_count(u64 low, u64 range) {
-  u32 k = 0;
-  while (((low ^ (low + range)) >> 56) == 0) {  // no_carry_expansion (:110-116)
-    low <<= 8;
-    range <<= 8;
-    ++k;
-  }
-  while (range < TOP16) {  // range_reduction_expansion (:126-135)
-    range = ~low & (TOP16 - 1);
-    low <<= 8;
-    range <<= 8;
-    ++k;
-  }
-  return k;
-}
-
-// byte store into the body's block: global memory (the launch path) or LDS (the service; the
-// pointer is generic, derived from the LDS block, and the compiler infers the address space)
-template <bool kLds>
-static __device__ __forceinline__ void bstore(uint8_t* p, u32 v) {
-  if constexpr (kLds) *p = (uint8_t)v;
-  else gstore8(p, v);
-}
-
-// Encoder::encode x n (+ finish) for stream k (the body of k_stream_encode and of the service)
+// Encoder::encode x n (+ finish) for stream k on its triples (the body of k_stream_encode and
+// of the service)
 template <bool kLds>
 static __device__ void stream_encode_one(
     u32 k, rc_stream_state* __restrict__ st, const u32* __restrict__ trip,
     const u64* __restrict__ sym_off, uint8_t* __restrict__ out, const u64* __restrict__ out_off,
     u64* __restrict__ out_len, uint8_t* __restrict__ nbytes, u32 finish,
     u32* __restrict__ flags) {
-  rc_stream_state S = st[k];
-  const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
-  uint8_t* o = out + out_off[k];
-  const u64 cap = out_off[k + 1] - out_off[k];
-  out_len[k] = 0;
-  if (S.flags) {  // the reference panicked (or hung) at an earlier call
-    flags[k] = S.flags;
-    return;
-  }
-  if (S.stage == 2) {  // Encoder::finish took the encoder by value (encoder.rs:40)
-    S.flags = RC_F_FINISHED;
-    st[k] = S;
-    flags[k] = S.flags;
-    return;
-  }
-  if (cap < RC_STREAM_MAX_BYTES(n, finish)) {  // not sticky: the caller retries, nothing changed
-    flags[k] = RC_F_CAPACITY;
-    return;
-  }
-  u64 low = S.lower_bound, range = S.range, w = 0;
-  for (u64 i = 0; i < n; ++i) {  // Encoder::encode (encoder.rs:24-37)
-    const u32* t = trip + 3 * (s0 + i);
-    const Narrow q = narrow(low, range, t[0], t[1], t[2], RC_F_ZERO_FREQ);
-    if (q.err) {
-      S.flags = q.err;
-      break;
-    }
-    low = q.low;
-    range = q.range;
-    u32 nb = 0;
-    while (((low ^ (low + range)) >> 56) == 0) {  // no_carry_expansion (:110-116)
-      bstore<kLds>(o + w++, (u32)(low >> 56));  // left_shift (:95-100)
-      low <<= 8;
-      range <<= 8;
-      ++nb;
-    }
-    while (range < TOP16) {  // range_reduction_expansion (:126-135)
-      range = ~low & (TOP16 - 1);
-      bstore<kLds>(o + w++, (u32)(low >> 56));
-      low <<= 8;
-      range <<= 8;
-      ++nb;
-    }
-    if (nbytes) bstore<kLds>(nbytes + s0 + i, nb);  // encode()'s return value (encoder.rs:34-36)
-    S.n += 1;
-  }
-  if (finish && !S.flags) {  // Encoder::finish: 8 x left_shift (encoder.rs:40-46)
-    for (int j = 0; j < 8; ++j) {
-      bstore<kLds>(o + w++, (u32)(low >> 56));
-      low <<= 8;
-      range <<= 8;
-    }
-    S.stage = 2;
-  } else if (S.stage == 0) {
-    S.stage = 1;
-  }
-  S.lower_bound = low;
-  S.range = range;
-  S.pos += w;
-  st[k] = S;
-  out_len[k] = w;
-  flags[k] = S.flags;
+  stream_encode_body<kLds>(k, st, sym_off, out, out_off, out_len, nbytes, finish, flags,
+                           [trip](u64 low, u64 range, u64 s0, u64 i) {
+                             const u32* t = trip + 3 * (s0 + i);
+                             return narrow(low, range, t[0], t[1], t[2], RC_F_ZERO_FREQ);
+                           });
 }
 
 __global__ __launch_bounds__(RWG) void k_stream_encode(
@@ -247,6 +130,7 @@ static __device__ void stream_decode_one(
     }
     low = q.low;
     range = q.range;
+    // (the loops again, not one helper that counts and applies: that changed this kernel's code)
     while (((low ^ (low + range)) >> 56) == 0) {
       low <<= 8;
       range <<= 8;
@@ -669,6 +553,92 @@ bool svc_call(const rc_ctx* ctx, Svc* sv, int dev, Fill fill, rc_status* err) {
   }
 }
 
+// The request block of one rc_stream_encode_host call, laid out from the call's arguments: the
+// mailbox block of the service and the staging block of the launch path are this one layout.
+//   state | offsets (sym_off[0..1], out_off[0..1]) | out_len | flags | triples || nbytes | out
+// The kernel reads [0, o_nb); it writes into the head [0, o_tr) and the tail [o_nb, + tail).
+struct EncBlock {
+  rc_stream_state* state;
+  const u32* triples;
+  u64 n, need;
+  uint8_t* out;
+  u64* out_len;
+  uint8_t* nbytes;
+  u32* flags_out;
+  size_t o_off = 64, o_len = o_off + 32, o_fl = o_len + 16, o_tr = o_fl + 16;
+  size_t o_nb = o_tr + ((12 * n + 15) & ~15ull), o_out = o_nb + ((n + 15) & ~15ull);
+  size_t tail = (o_out + need - o_nb + 15) & ~15ull;
+
+  void fill(char* h) const {
+    memcpy(h, state, sizeof *state);
+    const u64 offs[4] = {0, n, 0, need};  // sym_off[0..1], out_off[0..1]
+    memcpy(h + o_off, offs, sizeof offs);
+    if (n) memcpy(h + o_tr, triples, 12 * n);
+  }
+  // the head's results; false: not what the kernel can have written
+  bool head(const char* h, rc_stream_state* nst, u64* w, u32* fl) const {
+    memcpy(nst, h, sizeof *nst);
+    memcpy(w, h + o_len, 8);
+    memcpy(fl, h + o_fl, 4);
+    return *w <= need && nst->n - state->n <= n;
+  }
+  // everything back to the caller (the head, and the tail's bytes and counts, are in h)
+  rc_status take(const char* h) const {
+    rc_stream_state nst;
+    u64 w;
+    u32 fl;
+    if (!head(h, &nst, &w, &fl)) return RC_E_DEVICE;
+    if (w) memcpy(out, h + o_out, w);
+    if (nbytes && n) memcpy(nbytes, h + o_nb, nst.n - state->n);
+    *state = nst;
+    *out_len = w;
+    if (flags_out) *flags_out = fl;
+    return fl ? RC_E_CHUNK : RC_OK;
+  }
+};
+
+// The same for one rc_stream_decode_host call.  The window is the code this call can read:
+// wlen bytes from stream position p0, so the state travels with pos relative to p0.
+//   state | offsets: code_off, code_len, sym_off[0..1] | flags | c | cum | window || syms
+// The kernel reads [0, o_win + wlen); it writes into the head [0, o_c) and the tail [o_sym, +tail).
+struct DecBlock {
+  rc_stream_state* state;
+  const u32 *c, *cum;
+  u32 n_symbols;
+  const uint8_t* code;
+  u64 p0, wlen;
+  uint8_t* syms;
+  u64 n;
+  u32* flags_out;
+  size_t o_off = 64, o_fl = o_off + 32, o_c = o_fl + 16, o_cum = o_c + 1024;
+  size_t o_win = o_cum + 1024, o_sym = o_win + ((wlen + 15) & ~15ull);
+  size_t tail = (n + 15) & ~15ull;
+
+  void fill(char* h) const {
+    rc_stream_state rel = *state;
+    rel.pos -= p0;  // the window starts at p0 (stage 0: at the stream start)
+    memcpy(h, &rel, sizeof rel);
+    const u64 offs[4] = {0, wlen, 0, n};
+    memcpy(h + o_off, offs, sizeof offs);
+    memcpy(h + o_c, c, 4ull * n_symbols);
+    memcpy(h + o_cum, cum, 4ull * n_symbols);
+    if (wlen) memcpy(h + o_win, code + p0, wlen);
+  }
+  rc_status take(const char* h) const {
+    rc_stream_state nst;
+    u32 fl;
+    memcpy(&nst, h, sizeof nst);
+    memcpy(&fl, h + o_fl, 4);
+    const u64 got = nst.n - state->n;
+    if (got > n) return RC_E_DEVICE;
+    if (got) memcpy(syms, h + o_sym, got);
+    nst.pos += p0;
+    *state = nst;
+    if (flags_out) *flags_out = fl;
+    return fl ? RC_E_CHUNK : RC_OK;
+  }
+};
+
 }  // namespace
 
 // Every launch of a batch kernel by the library first asks the process's running service waves
@@ -739,95 +709,64 @@ rc_status rc_stream_encode_host(rc_ctx* ctx, rc_stream_state* state, const uint3
     if (flags_out) *flags_out = RC_F_CAPACITY;
     return RC_E_CAPACITY;
   }
-  // block: state | offsets (4 x u64) | out_len | flags | triples || nbytes | out
-  const size_t o_off = 64, o_len = o_off + 32, o_fl = o_len + 16, o_tr = o_fl + 16;
-  const size_t o_nb = o_tr + ((12 * n + 15) & ~15ull), o_out = o_nb + ((n + 15) & ~15ull);
-  const size_t tail = (o_out + need - o_nb + 15) & ~15ull;
-  if (svc_enabled(ctx) && o_nb + tail <= SVC_BLOCK) {  // a small call: through the stream service
+  const EncBlock b{state, triples, n, need, out, out_len, nbytes, flags_out};
+  if (svc_enabled(ctx) && b.o_nb + b.tail <= SVC_BLOCK) {  // a small call: through the service
     auto sv = svc_get(ctx);
     std::lock_guard<std::mutex> slk(sv->mu);
     rc_status err = RC_OK;
-    if (svc_call(ctx, sv.get(), dev, [&](char* h, SvcBox* b) {
-          memcpy(h, state, sizeof *state);
-          const u64 offs[4] = {0, n, 0, need};
-          memcpy(h + o_off, offs, sizeof offs);
-          if (n) memcpy(h + o_tr, triples, 12 * n);
-          b->op = SVC_ENCODE;
-          b->finish = finish;
-          b->in_bytes = o_nb;
-          b->head_bytes = o_tr;
-          b->tail_off = o_nb;
-          b->tail_bytes = tail;
-          const u64 o[8] = {o_off, o_len, o_fl, o_tr, o_nb, o_out, nbytes ? 1u : 0u, 0};
-          memcpy(b->o, o, sizeof o);
-        }, &err)) {
-      if (err != RC_OK) return err;
-      const char* h = (const char*)(sv->box + 1);
-      rc_stream_state nst;
-      memcpy(&nst, h, sizeof nst);
-      u64 w;
-      u32 fl;
-      memcpy(&w, h + o_len, 8);
-      memcpy(&fl, h + o_fl, 4);
-      if (w > need || nst.n - state->n > n) return RC_E_DEVICE;
-      if (w) memcpy(out, h + o_out, w);
-      if (nbytes && n) memcpy(nbytes, h + o_nb, nst.n - state->n);
-      *state = nst;
-      *out_len = w;
-      if (flags_out) *flags_out = fl;
-      return fl ? RC_E_CHUNK : RC_OK;
-    }
+    if (svc_call(ctx, sv.get(), dev, [&](char* h, SvcBox* sb) {
+          b.fill(h);
+          sb->op = SVC_ENCODE;
+          sb->finish = finish;
+          sb->in_bytes = b.o_nb;
+          sb->head_bytes = b.o_tr;
+          sb->tail_off = b.o_nb;
+          sb->tail_bytes = b.tail;
+          const u64 o[8] = {b.o_off, b.o_len, b.o_fl, b.o_tr, b.o_nb, b.o_out, nbytes ? 1u : 0u, 0};
+          memcpy(sb->o, o, sizeof o);
+        }, &err))
+      return err != RC_OK ? err : b.take((const char*)(sv->box + 1));
   }
   DeviceGuard g(dev);  // (the service path makes no HIP call but its wave's launch, guarded there)
   char* d = nullptr;
   std::shared_ptr<Stage> keep;
   std::unique_lock<std::mutex> lk;
-  char* h = stage_acquire(ctx, o_out + need, &d, &keep, &lk);
+  char* h = stage_acquire(ctx, b.o_out + need, &d, &keep, &lk);
   if (!h) return RC_E_DEVICE;
-  memcpy(h, state, sizeof *state);
-  const u64 offs[4] = {0, n, 0, need};  // sym_off[0..1], out_off[0..1]
-  memcpy(h + o_off, offs, sizeof offs);
-  if (n) memcpy(h + o_tr, triples, 12 * n);
-  if (hipMemcpyAsync(d, h, o_nb, hipMemcpyHostToDevice, s) != hipSuccess) return RC_E_DEVICE;
+  b.fill(h);
+  if (hipMemcpyAsync(d, h, b.o_nb, hipMemcpyHostToDevice, s) != hipSuccess) return RC_E_DEVICE;
   hipLaunchKernelGGL(k_stream_encode, dim3(1), dim3(RWG), 0, s, (rc_stream_state*)d,
-                     (const u32*)(d + o_tr), (const u64*)(d + o_off), 1u, (uint8_t*)(d + o_out),
-                     (const u64*)(d + o_off + 16), (u64*)(d + o_len),
-                     nbytes ? (uint8_t*)(d + o_nb) : (uint8_t*)nullptr, finish,
-                     (u32*)(d + o_fl));
+                     (const u32*)(d + b.o_tr), (const u64*)(d + b.o_off), 1u,
+                     (uint8_t*)(d + b.o_out), (const u64*)(d + b.o_off + 16), (u64*)(d + b.o_len),
+                     nbytes ? (uint8_t*)(d + b.o_nb) : (uint8_t*)nullptr, finish,
+                     (u32*)(d + b.o_fl));
   if (hipGetLastError() != hipSuccess) return RC_E_DEVICE;
   // state, out_len and flags, then the new bytes (and the counts, when asked for).  A large
   // call reads the state first and then only the w bytes written, not the 12n + 8 worst case.
   const bool two_phase = need > kTwoPhaseBytes;
-  if (hipMemcpyAsync(h, d, o_tr, hipMemcpyDeviceToHost, s) != hipSuccess) return RC_E_DEVICE;
+  if (hipMemcpyAsync(h, d, b.o_tr, hipMemcpyDeviceToHost, s) != hipSuccess) return RC_E_DEVICE;
   if (!two_phase) {
     if ((nbytes && n &&
-         hipMemcpyAsync(h + o_nb, d + o_nb, n, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        (need && hipMemcpyAsync(h + o_out, d + o_out, need, hipMemcpyDeviceToHost, s) !=
+         hipMemcpyAsync(h + b.o_nb, d + b.o_nb, n, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        (need && hipMemcpyAsync(h + b.o_out, d + b.o_out, need, hipMemcpyDeviceToHost, s) !=
                      hipSuccess))
       return RC_E_DEVICE;
   }
   if (hipStreamSynchronize(s) != hipSuccess) return RC_E_DEVICE;
-  rc_stream_state nst;
-  memcpy(&nst, h, sizeof nst);
-  u64 w;
-  u32 fl;
-  memcpy(&w, h + o_len, 8);
-  memcpy(&fl, h + o_fl, 4);
-  if (w > need || nst.n - state->n > n) return RC_E_DEVICE;
   if (two_phase) {
+    rc_stream_state nst;
+    u64 w;
+    u32 fl;
+    if (!b.head(h, &nst, &w, &fl)) return RC_E_DEVICE;
     const u64 got = nst.n - state->n;
     if ((nbytes && got &&
-         hipMemcpyAsync(h + o_nb, d + o_nb, got, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        (w && hipMemcpyAsync(h + o_out, d + o_out, w, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+         hipMemcpyAsync(h + b.o_nb, d + b.o_nb, got, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        (w && hipMemcpyAsync(h + b.o_out, d + b.o_out, w, hipMemcpyDeviceToHost, s) !=
+                  hipSuccess) ||
         hipStreamSynchronize(s) != hipSuccess)
       return RC_E_DEVICE;
   }
-  if (w) memcpy(out, h + o_out, w);
-  if (nbytes && n) memcpy(nbytes, h + o_nb, nst.n - state->n);
-  *state = nst;
-  *out_len = w;
-  if (flags_out) *flags_out = fl;
-  return fl ? RC_E_CHUNK : RC_OK;
+  return b.take(h);
 }
 
 rc_status rc_stream_decode_host(rc_ctx* ctx, const uint32_t* c, const uint32_t* cum,
@@ -842,85 +781,46 @@ rc_status rc_stream_decode_host(rc_ctx* ctx, const uint32_t* c, const uint32_t* 
   const u64 p0 = state->stage == 0 ? 0 : state->pos;
   if (p0 > code_len) return RC_E_ARG;
   const u64 wlen = std::min<u64>(code_len - p0, (state->stage == 0 ? 8 : 0) + 12 * n);
-  // block: state | offsets: code_off, code_len, sym_off[0..1] | flags | c | cum | window || syms
-  const size_t o_off = 64, o_fl = o_off + 32, o_c = o_fl + 16, o_cum = o_c + 1024;
-  const size_t o_win = o_cum + 1024, o_sym = o_win + ((wlen + 15) & ~15ull);
-  const size_t tail = (n + 15) & ~15ull;
-  if (svc_enabled(ctx) && o_sym + tail <= SVC_BLOCK) {  // a small call: through the stream service
+  const DecBlock b{state, c, cum, n_symbols, code, p0, wlen, syms, n, flags_out};
+  if (svc_enabled(ctx) && b.o_sym + b.tail <= SVC_BLOCK) {  // a small call: through the service
     auto sv = svc_get(ctx);
     std::lock_guard<std::mutex> slk(sv->mu);
     rc_status err = RC_OK;
-    if (svc_call(ctx, sv.get(), dev, [&](char* h, SvcBox* b) {
-          rc_stream_state rel = *state;
-          rel.pos -= p0;  // the window starts at p0 (stage 0: at the stream start)
-          memcpy(h, &rel, sizeof rel);
-          const u64 offs[4] = {0, wlen, 0, n};
-          memcpy(h + o_off, offs, sizeof offs);
-          memcpy(h + o_c, c, 4ull * n_symbols);
-          memcpy(h + o_cum, cum, 4ull * n_symbols);
-          if (wlen) memcpy(h + o_win, code + p0, wlen);
-          b->op = SVC_DECODE;
-          b->n_alpha = n_symbols;
-          b->total = total_freq;
-          b->in_bytes = o_sym;
-          b->head_bytes = o_c;
-          b->tail_off = o_sym;
-          b->tail_bytes = tail;
-          const u64 o[8] = {o_off, o_fl, o_c, o_cum, o_win, o_sym, 0, 0};
-          memcpy(b->o, o, sizeof o);
-        }, &err)) {
-      if (err != RC_OK) return err;
-      const char* h = (const char*)(sv->box + 1);
-      rc_stream_state nst;
-      u32 fl;
-      memcpy(&nst, h, sizeof nst);
-      memcpy(&fl, h + o_fl, 4);
-      const u64 got = nst.n - state->n;
-      if (got > n) return RC_E_DEVICE;
-      if (got) memcpy(syms, h + o_sym, got);
-      nst.pos += p0;
-      *state = nst;
-      if (flags_out) *flags_out = fl;
-      return fl ? RC_E_CHUNK : RC_OK;
-    }
+    if (svc_call(ctx, sv.get(), dev, [&](char* h, SvcBox* sb) {
+          b.fill(h);
+          sb->op = SVC_DECODE;
+          sb->n_alpha = n_symbols;
+          sb->total = total_freq;
+          sb->in_bytes = b.o_sym;
+          sb->head_bytes = b.o_c;
+          sb->tail_off = b.o_sym;
+          sb->tail_bytes = b.tail;
+          const u64 o[8] = {b.o_off, b.o_fl, b.o_c, b.o_cum, b.o_win, b.o_sym, 0, 0};
+          memcpy(sb->o, o, sizeof o);
+        }, &err))
+      return err != RC_OK ? err : b.take((const char*)(sv->box + 1));
   }
   DeviceGuard g(dev);
   char* d = nullptr;
   std::shared_ptr<Stage> keep;
   std::unique_lock<std::mutex> lk;
-  char* h = stage_acquire(ctx, o_sym + n, &d, &keep, &lk);
+  char* h = stage_acquire(ctx, b.o_sym + n, &d, &keep, &lk);
   if (!h) return RC_E_DEVICE;
-  rc_stream_state rel = *state;
-  rel.pos -= p0;  // the window starts at p0 (stage 0: at the stream start)
-  memcpy(h, &rel, sizeof rel);
-  const u64 offs[4] = {0, wlen, 0, n};
-  memcpy(h + o_off, offs, sizeof offs);
-  memcpy(h + o_c, c, 4ull * n_symbols);
-  memcpy(h + o_cum, cum, 4ull * n_symbols);
-  if (wlen) memcpy(h + o_win, code + p0, wlen);
-  if (hipMemcpyAsync(d, h, o_win + wlen, hipMemcpyHostToDevice, s) != hipSuccess)
+  b.fill(h);
+  if (hipMemcpyAsync(d, h, b.o_win + wlen, hipMemcpyHostToDevice, s) != hipSuccess)
     return RC_E_DEVICE;
-  hipLaunchKernelGGL(k_stream_decode, dim3(1), dim3(RWG), 0, s, (const u32*)(d + o_c),
-                     (const u32*)(d + o_cum), n_symbols, total_freq, (rc_stream_state*)d,
-                     (const uint8_t*)(d + o_win), (const u64*)(d + o_off),
-                     (const u64*)(d + o_off + 8), (uint8_t*)(d + o_sym),
-                     (const u64*)(d + o_off + 16), 1u, (u32*)(d + o_fl));
+  hipLaunchKernelGGL(k_stream_decode, dim3(1), dim3(RWG), 0, s, (const u32*)(d + b.o_c),
+                     (const u32*)(d + b.o_cum), n_symbols, total_freq, (rc_stream_state*)d,
+                     (const uint8_t*)(d + b.o_win), (const u64*)(d + b.o_off),
+                     (const u64*)(d + b.o_off + 8), (uint8_t*)(d + b.o_sym),
+                     (const u64*)(d + b.o_off + 16), 1u, (u32*)(d + b.o_fl));
   if (hipGetLastError() != hipSuccess) return RC_E_DEVICE;
-  if (hipMemcpyAsync(h, d, o_c, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      (n && hipMemcpyAsync(h + o_sym, d + o_sym, n, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+  if (hipMemcpyAsync(h, d, b.o_c, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      (n && hipMemcpyAsync(h + b.o_sym, d + b.o_sym, n, hipMemcpyDeviceToHost, s) !=
+                hipSuccess) ||
       hipStreamSynchronize(s) != hipSuccess)
     return RC_E_DEVICE;
-  rc_stream_state nst;
-  u32 fl;
-  memcpy(&nst, h, sizeof nst);
-  memcpy(&fl, h + o_fl, 4);
-  const u64 got = nst.n - state->n;
-  if (got > n) return RC_E_DEVICE;
-  if (got) memcpy(syms, h + o_sym, got);
-  nst.pos += p0;
-  *state = nst;
-  if (flags_out) *flags_out = fl;
-  return fl ? RC_E_CHUNK : RC_OK;
+  return b.take(h);
 }
 
 // Internal (not in include/range_coder.h; tools/percall_native.cpp): the context's stream-service

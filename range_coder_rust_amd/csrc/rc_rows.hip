@@ -19,16 +19,12 @@
 // Decode, many streams (k_stream_decode_rows_lane): one lane per stream, the
 // row walked in device memory by the lane itself; rows_decode_plan picks between the two.
 //
-// Encode: one lane per stream, rc_resume.hip's encoder body with the triple gathered from the
-// rows.  The arithmetic of both is the reference's, branch for branch (see rc_resume.hip).
+// Encode: one lane per stream, the shared encoder body with the triple gathered from the rows.
 //
-// The helpers below restate rc_resume.hip's (narrow_r, settle_count): that unit stays as it is,
-// so that its kernels' code does not change with this one's callers.
-#include "rc_host.h"
-#include "rc_udiv.h"
-
-#define RWG 64
-#define TOP8 (1ull << 56)  // range_coder.rs:23
+// The coder step (narrow_r and its sticky flags), the byte count of the renormalisation loops and
+// the encoder body are rc_stream_dev.h's, shared with rc_resume.hip: the arithmetic of every
+// stream kernel is the reference's, branch for branch, and is written once.
+#include "rc_stream_dev.h"
 
 #ifndef RC_ROWS_D
 #define RC_ROWS_D 4  // prefetch depth in symbols: 1, 2, 4 or 8 (the sweep)
@@ -37,27 +33,6 @@ static_assert(RC_ROWS_D == 1 || RC_ROWS_D == 2 || RC_ROWS_D == 4 || RC_ROWS_D ==
               "the ring's slot of symbol i is i % RC_ROWS_D in every 64-symbol block");
 
 namespace {
-
-// RangeCoder::param_update up to the renormalisation loops: the narrowed interval, or a flag
-struct Narrow {
-  u64 low, range;
-  u32 err;
-};
-
-// (r = range_par_total, range_coder.rs:38-40)
-static __device__ __forceinline__ Narrow narrow_r(u64 low, u64 range, u64 r, u32 c, u32 cum,
-                                                  u32 zero_flag) {
-  Narrow o{low, range, 0u};
-  const u64 nr = r * (u64)c;     // range_coder.rs:65
-  const u64 add = r * (u64)cum;  // :68
-  const u64 nl = low + add;
-  if (nl < add) o.err = RC_F_BAD_MODEL;          // overflowing_add -> Err (:68-81)
-  else if (nr == 0) o.err = zero_flag;           // no_carry_expansion never terminates
-  else if (nl + nr < nr) o.err = RC_F_BAD_MODEL;  // upper_bound() overflow (:138-146)
-  o.low = nl;
-  o.range = nr;
-  return o;
-}
 
 static __device__ __forceinline__ u32 rfl(u32 v) { return __builtin_amdgcn_readfirstlane(v); }
 static __device__ __forceinline__ u64 rfl64(u64 v) {
@@ -247,6 +222,7 @@ __global__ __launch_bounds__(RWG) void k_stream_decode_rows(
           sflags = q.err;
           break;
         }
+        // (counted inline: one count-and-apply helper for the decoders changed this kernel's code)
         u64 nl = q.low, nr = q.range;
         u32 nb = 0;
         while (((nl ^ (nl + nr)) >> 56) == 0) {  // no_carry_expansion (:110-116)
@@ -432,6 +408,7 @@ __global__ __launch_bounds__(RWG) void k_stream_decode_rows_lane(
       sflags = q.err;
       break;
     }
+    // (counted inline: one count-and-apply helper for the decoders changed this kernel's code)
     u64 nl = q.low, nr = q.range;
     u32 nb = 0;
     while (((nl ^ (nl + nr)) >> 56) == 0) {  // no_carry_expansion (:110-116)
@@ -470,8 +447,8 @@ __global__ __launch_bounds__(RWG) void k_stream_decode_rows_lane(
   flags[k] = sflags;
 }
 
-// Encoder::encode x n (+ finish) for stream k: rc_resume.hip's stream_encode_one with the triple
-// gathered from the rows
+// Encoder::encode x n (+ finish) for stream k: the shared body with the triple gathered from the
+// rows.  The step's checks keep this order: the row, the symbol, the row's total.
 __global__ __launch_bounds__(RWG) void k_stream_encode_rows(
     const u32* __restrict__ c_tab, const u32* __restrict__ cum_tab,
     const u32* __restrict__ total_tab, u32 n_rows, u32 n_alpha, const u32* __restrict__ row_of,
@@ -482,84 +459,20 @@ __global__ __launch_bounds__(RWG) void k_stream_encode_rows(
   const u32 k = blockIdx.x * RWG + threadIdx.x;
   if (k >= n_streams) return;
   RC_VGPR_FLOOR_48();
-  rc_stream_state S = st[k];
-  const u64 s0 = sym_off[k], n = sym_off[k + 1] - s0;
-  uint8_t* o = out + out_off[k];
-  const u64 cap = out_off[k + 1] - out_off[k];
-  out_len[k] = 0;
-  if (S.flags) {  // the reference panicked (or hung) at an earlier call
-    flags[k] = S.flags;
-    return;
-  }
-  if (S.stage == 2) {  // Encoder::finish took the encoder by value (encoder.rs:40)
-    S.flags = RC_F_FINISHED;
-    st[k] = S;
-    flags[k] = S.flags;
-    return;
-  }
-  if (cap < RC_STREAM_MAX_BYTES(n, finish)) {  // not sticky: the caller retries, nothing changed
-    flags[k] = RC_F_CAPACITY;
-    return;
-  }
-  u64 low = S.lower_bound, range = S.range, w = 0;
-  for (u64 i = 0; i < n; ++i) {  // Encoder::encode (encoder.rs:24-37)
-    const u32 row = gload(row_of + s0 + i);
-    if (row >= n_rows) {
-      S.flags = RC_F_BAD_MODEL;
-      break;
-    }
-    const u32 sym = syms[s0 + i];
-    if (sym >= n_alpha) {  // c_freq(index) panics (sample_impl.rs:19)
-      S.flags = RC_F_BAD_SYMBOL;
-      break;
-    }
-    const u64 e = (u64)row * n_alpha + sym;
-    const u32 total = gload(total_tab + row);
-    if (total == 0) {  // range_par_total divides by 0
-      S.flags = RC_F_BAD_MODEL;
-      break;
-    }
-    const Narrow q = narrow_r(low, range, rc_udiv64(range, total), gload(c_tab + e),
-                              gload(cum_tab + e), RC_F_ZERO_FREQ);
-    if (q.err) {
-      S.flags = q.err;
-      break;
-    }
-    low = q.low;
-    range = q.range;
-    u32 nb = 0;
-    while (((low ^ (low + range)) >> 56) == 0) {  // no_carry_expansion (:110-116)
-      gstore8(o + w++, (u32)(low >> 56));  // left_shift (:95-100)
-      low <<= 8;
-      range <<= 8;
-      ++nb;
-    }
-    while (range < TOP16) {  // range_reduction_expansion (:126-135)
-      range = ~low & (TOP16 - 1);
-      gstore8(o + w++, (u32)(low >> 56));
-      low <<= 8;
-      range <<= 8;
-      ++nb;
-    }
-    if (nbytes) gstore8(nbytes + s0 + i, nb);  // encode()'s return value (encoder.rs:34-36)
-    S.n += 1;
-  }
-  if (finish && !S.flags) {  // Encoder::finish: 8 x left_shift (encoder.rs:40-46)
-    for (int j = 0; j < 8; ++j) {
-      gstore8(o + w++, (u32)(low >> 56));
-      low <<= 8;
-      range <<= 8;
-    }
-    S.stage = 2;
-  } else if (S.stage == 0) {
-    S.stage = 1;
-  }
-  S.lower_bound = low;
-  S.range = range;
-  S.pos += w;
-  st[k] = S;
-  out_len[k] = w;
-  flags[k] = S.flags;
+  stream_encode_body<false>(
+      k, st, sym_off, out, out_off, out_len, nbytes, finish, flags,
+      [=](u64 low, u64 range, u64 s0, u64 i) {
+        const u32 row = gload(row_of + s0 + i);
+        if (row >= n_rows) return Narrow{low, range, RC_F_BAD_MODEL};
+        const u32 sym = syms[s0 + i];
+        // c_freq(index) panics (sample_impl.rs:19)
+        if (sym >= n_alpha) return Narrow{low, range, RC_F_BAD_SYMBOL};
+        const u64 e = (u64)row * n_alpha + sym;
+        const u32 total = gload(total_tab + row);
+        if (total == 0) return Narrow{low, range, RC_F_BAD_MODEL};  // range_par_total divides by 0
+        return narrow_r(low, range, rc_udiv64(range, total), gload(c_tab + e), gload(cum_tab + e),
+                        RC_F_ZERO_FREQ);
+      });
 }
 
 // Which decoder a launch takes: 0 the wave-per-stream kernel, 1 the lane-per-stream kernel
