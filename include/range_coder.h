@@ -215,6 +215,80 @@ rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_
                                   const uint64_t* sym_off_dev, uint32_t n_chunks,
                                   uint32_t* flags_dev);
 
+/* ---- static chunk sets: a model chosen per chunk ----
+ * A batch is often a mixture (weights beside indices, text beside binary), which one pooled
+ * table prices badly.  A chunk set holds n_models static tables over one alphabet and one
+ * total_freq, and the chunk-set batch calls take one class per CHUNK: chunk k is coded exactly as
+ * rc_encode_batch / rc_decode_batch code it with rc_model_create_static(row class_of[k]) --
+ * bytes, out_len, flags, the capacity rule and RC_F_TOO_LONG, and for the decoder garbage and
+ * truncated streams judged against that row.  The launch is sorted by class on the device, every
+ * workgroup stages one row and runs the single-table symbol step, so
+ * the cost over the single-table calls is the sort and at most n_models partly filled workgroups.
+ *
+ * Accepted inputs are exactly rc_model_create_static_set's (1 <= n_models <= RC_MAX_SET_MODELS,
+ * 1 <= n_symbols <= 256, 256 <= total_freq <= 65536 shared by the rows, every row passing
+ * rc_model_create_static's checks); anything else is RC_E_BAD_MODEL.  A chunk set is its own kind
+ * of rc_model: the chunk-set calls take nothing else (RC_E_ARG), and every other entry point that
+ * takes a model returns RC_E_ARG for a chunk set.  Destroy it with rc_model_destroy.  A set and
+ * its class_of travel beside the code: the containers do not carry them.                      */
+rc_status rc_model_create_chunk_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                    const uint32_t* c_freq_host,   /* n_models x n_symbols */
+                                    const uint32_t* cum_freq_host, /* likewise */
+                                    uint32_t total_freq, rc_model** out);
+/* rc_encode_batch with a row per chunk.
+ * class_of_dev  one byte per chunk: the row of chunk k.  class_of[k] >= n_models gives that chunk
+ *               RC_F_BAD_MODEL and out_len 0; its slot is not written and its symbols are not
+ *               read, and every other chunk is unaffected.
+ * Everything else as rc_encode_batch with that row's static model.  Asynchronous and
+ * stream-ordered on the context's stream; nothing synchronises with the host.  The context keeps
+ * the launch's grouping in a scratch buffer of its own, which grows in stream order; a call on
+ * another stream than the context's last chunk-set call waits on the device for that call's
+ * coder before it regroups, so a context may change streams between calls (rc_ctx_set_stream).
+ * As with every entry point, one context is used by one host thread at a time.               */
+rc_status rc_encode_batch_chunk_set(rc_ctx* ctx, const rc_model* set,
+                                    const uint8_t* class_of_dev, const uint8_t* syms_dev,
+                                    const uint64_t* sym_off_dev, uint32_t n_chunks,
+                                    uint8_t* out_dev, const uint64_t* out_off_dev,
+                                    uint64_t* out_len_dev, uint32_t* flags_dev);
+/* rc_decode_batch with a row per chunk (side information, known before decoding).
+ * class_of_dev  as above; class_of[k] >= n_models gives that chunk RC_F_BAD_MODEL, and its
+ *               symbols are not written.
+ * Everything else, the over-read of the code included, as rc_decode_batch with that row's static
+ * model.                                                                                     */
+rc_status rc_decode_batch_chunk_set(rc_ctx* ctx, const rc_model* set,
+                                    const uint8_t* class_of_dev, const uint8_t* code_dev,
+                                    const uint64_t* code_off_dev, const uint64_t* code_len_dev,
+                                    uint8_t* syms_out_dev, const uint64_t* sym_off_dev,
+                                    uint32_t n_chunks, uint32_t* flags_dev);
+/* Fitting the classes of a chunk set.  Costs are integers in units of 2^-16 bit, so every result
+ * is exact.
+ * rc_cost_table (host only): cost_out_host[s] = round(65536 * log2(total_freq / c_freq[s])), and
+ * RC_COST_NONE where c_freq[s] == 0 (the row cannot code s).  RC_E_ARG: a null pointer,
+ * n_symbols outside 1..256, total_freq == 0, a c_freq above total_freq.                      */
+#define RC_COST_NONE 0xFFFFFFFFu
+rc_status rc_cost_table(const uint32_t* c_freq_host, uint32_t n_symbols, uint32_t total_freq,
+                        uint32_t* cost_out_host /* n_symbols */);
+/* The cost of every chunk under every row, and the cheapest row.
+ * chunk_hist_dev  n_chunks x 256 counts, rc_histogram's rows (16-byte aligned)
+ * cost_host       n_models x 256 entries, taken as given (rc_cost_table's; entries past a row's
+ *                 alphabet: RC_COST_NONE)
+ * best_row_dev    n_chunks bytes: the row of the least cost, ties to the lowest row
+ * best_cost_dev   n_chunks x u64: that cost
+ * costs_dev       NULL, or n_chunks x n_models u64: every cost
+ * The cost of chunk k under row r is the sum over s of hist[k][s] * cost[r][s] in 64 bits, and
+ * UINT64_MAX if the chunk counts a symbol whose entry is RC_COST_NONE.  Stream-ordered; returns
+ * after the table's upload (it waits for the context's stream).  RC_E_ARG: a null pointer (costs_dev
+ * aside), n_models outside 1..RC_MAX_SET_MODELS, n_chunks > RC_MAX_CHUNKS.                   */
+rc_status rc_chunk_set_costs(rc_ctx* ctx, const uint32_t* chunk_hist_dev, uint32_t n_chunks,
+                             const uint32_t* cost_host, uint32_t n_models, uint8_t* best_row_dev,
+                             uint64_t* best_cost_dev, uint64_t* costs_dev);
+/* The member chunks' rows summed per class: class_hist_dev[c][s] += the sum of hist[k][s] over the
+ * chunks with class_of[k] == c (n_models x 256 u64, ADDED into; a class id >= n_models is
+ * skipped).  Asynchronous and stream-ordered.  RC_E_ARG as above.                            */
+rc_status rc_histogram_by_class(rc_ctx* ctx, const uint32_t* chunk_hist_dev,
+                                const uint8_t* class_of_dev, uint32_t n_chunks, uint32_t n_models,
+                                uint64_t* class_hist_dev);
+
 /* ---- order-1 sets: the previous symbol picks the model (encoder.rs:24-37, decoder.rs:38-54) ----
  * The commonest context model: the table of symbol i is chosen by symbol i - 1.  The indexed calls
  * above can write such a stream (idx[i] = f(sym[i-1])) but not read it back, because the decoder

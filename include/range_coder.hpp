@@ -463,6 +463,93 @@ class ModelSet {
   uint32_t n_ = 0, total_ = 0;
 };
 
+// A static chunk set (rc_model_create_chunk_set): K tables over one alphabet and one total_freq,
+// and batch coding with a model chosen per CHUNK -- chunk k is coded exactly as a static Model of
+// row class_of[k] codes it.  The chunk-set entry points take device memory only, so the chunk
+// helpers stage through buffers they allocate with the HIP runtime.
+class ChunkSet {
+ public:
+  ChunkSet(Context& ctx, const std::vector<const PModel*>& models) : ctx_(&ctx) {
+    if (models.empty()) throw RangeCoderError("empty chunk set", RC_E_BAD_MODEL);
+    n_ = (uint32_t)models[0]->alphabet_count();
+    total_ = models[0]->total_freq();
+    for (const PModel* pm : models) {
+      if (pm->alphabet_count() != n_ || pm->total_freq() != total_)
+        throw RangeCoderError("the models of a set share one alphabet and one total_freq",
+                              RC_E_BAD_MODEL);
+      for (uint32_t i = 0; i < n_; ++i) {
+        c_.push_back(pm->c_freq(i));
+        cum_.push_back(pm->cum_freq(i));
+      }
+    }
+    check(rc_model_create_chunk_set(ctx.get(), (uint32_t)models.size(), n_, c_.data(),
+                                    cum_.data(), total_, &m_),
+          "rc_model_create_chunk_set");
+  }
+  ~ChunkSet() {
+    if (m_) rc_model_destroy(m_);
+  }
+  ChunkSet(const ChunkSet&) = delete;
+  ChunkSet& operator=(const ChunkSet&) = delete;
+  rc_model* get() const { return m_; }
+  Context& ctx() const { return *ctx_; }
+  uint64_t slot_capacity(uint64_t n) const { return detail::slot_capacity(c_, total_, n); }
+
+  // Encode many independent chunks in one launch, chunk k with row class_of[k].
+  std::vector<std::vector<uint8_t>> encode_chunks(
+      const std::vector<std::vector<uint8_t>>& chunks, const std::vector<uint8_t>& class_of) const {
+    const uint32_t n = (uint32_t)chunks.size();
+    if (class_of.size() != n) throw RangeCoderError("one class per chunk", RC_E_ARG);
+    std::vector<uint64_t> sym_off;
+    const auto syms = detail::concat<uint8_t>(
+        n, [&](uint32_t k) -> const std::vector<uint8_t>& { return chunks[k]; }, sym_off);
+    const detail::DevBuf d_cls(class_of);
+    return detail::encode_chunks(
+        ctx_->get(), syms, sym_off, [&](uint64_t len) { return slot_capacity(len); },
+        [&](const uint8_t* s, const uint64_t* soff, uint32_t nc, uint8_t* out,
+            const uint64_t* ooff, uint64_t* len, uint32_t* flags) {
+          check(rc_encode_batch_chunk_set(ctx_->get(), m_, d_cls.u8(), s, soff, nc, out, ooff,
+                                          len, flags),
+                "rc_encode_batch_chunk_set");
+        });
+  }
+
+  // Decode many independent streams: counts[k] symbols from codes[k] with row class_of[k] (the
+  // count is out-of-band, sample_impl.rs:113-120).
+  std::vector<std::vector<uint8_t>> decode_chunks(const std::vector<std::vector<uint8_t>>& codes,
+                                                  const std::vector<uint64_t>& counts,
+                                                  const std::vector<uint8_t>& class_of) const {
+    const uint32_t n = (uint32_t)codes.size();
+    if (class_of.size() != n || counts.size() != n)
+      throw RangeCoderError("one class and one count per chunk", RC_E_ARG);
+    const detail::DevBuf d_cls(class_of);
+    return detail::decode_chunks<uint8_t>(
+        ctx_->get(), n, [&](uint32_t k) -> const std::vector<uint8_t>& { return codes[k]; },
+        [&](uint32_t k) { return counts[k]; },
+        [&](const uint8_t* code, const uint64_t* coff, const uint64_t* clen, uint8_t* syms,
+            const uint64_t* soff, uint32_t nc, uint32_t* flags) {
+          check(rc_decode_batch_chunk_set(ctx_->get(), m_, d_cls.u8(), code, coff, clen, syms,
+                                          soff, nc, flags),
+                "rc_decode_batch_chunk_set");
+        });
+  }
+
+ private:
+  Context* ctx_;
+  rc_model* m_ = nullptr;
+  std::vector<uint32_t> c_, cum_;
+  uint32_t n_ = 0, total_ = 0;
+};
+
+// A row's integer costs for fitting a chunk set (rc_cost_table): round(65536 log2(total / c)),
+// RC_COST_NONE where c == 0.
+inline std::vector<uint32_t> cost_table(const std::vector<uint32_t>& c_freq, uint32_t total) {
+  std::vector<uint32_t> out(c_freq.size());
+  check(rc_cost_table(c_freq.data(), (uint32_t)c_freq.size(), total, out.data()),
+        "rc_cost_table");
+  return out;
+}
+
 // An order-1 set (rc_model_create_order1_set): K tables over one alphabet and one total_freq
 // plus a context map, and batch coding in which the previous symbol of the chunk picks the
 // table -- symbol 0 of a chunk is coded with models[first_row], symbol i > 0 as

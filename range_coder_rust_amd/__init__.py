@@ -15,6 +15,8 @@ from .api import (  # noqa: F401
     decode_chunks_order1,
     RowTable, stream_decode_rows_batch, stream_encode_rows_batch, encode_chunks_rows,
     decode_chunks_rows,
+    ChunkModelSet, encode_batch_chunk_set, decode_batch_chunk_set, encode_chunks_chunk_set,
+    decode_chunks_chunk_set,
 )
 from . import synth  # noqa: F401
 from .model_build import build_model, histogram, ideal_bits, quantize_counts, quantize_counts_wide  # noqa: F401
@@ -22,6 +24,8 @@ from .model_build import build_order1_set, histogram_order1  # noqa: F401
 from .model_build import build_wide_model, histogram_wide, ideal_bits_wide  # noqa: F401
 from .model_build import (cluster_contexts, cluster_contexts_joint, fit_order1_set,  # noqa: F401
                           histogram_pairs, histogram_pairs_periodic, ideal_bits_order1)
+from .model_build import (chunk_set_costs, cost_table, fit_chunk_set,  # noqa: F401
+                          histogram_by_class)
 from . import container  # noqa: F401
 from .container import (ChecksumError, ContainerError, checksum_batch, compress,  # noqa: F401
                         decompress)

@@ -49,6 +49,8 @@ EXPORTS = (
     "rc_container2_offsets", "rc_container2_model", "rc_container2_verify",
     "rc_cluster_contexts_dev",
     "rc_model_create_order1_set_lagged", "rc_histogram_pairs_lagged",
+    "rc_model_create_chunk_set", "rc_encode_batch_chunk_set", "rc_decode_batch_chunk_set",
+    "rc_cost_table", "rc_chunk_set_costs", "rc_histogram_by_class",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
@@ -257,8 +259,32 @@ def load():
         L.rc_model_order1_check_lagged_.restype = _I
         L.rc_model_order1_plan_lagged_.argtypes = [_U32, _U32, _U32, _U32, _P]
         L.rc_model_order1_plan_lagged_.restype = _I
+    # static chunk sets (a library of an earlier revision has none of these)
+    cset = ("rc_model_create_chunk_set", "rc_encode_batch_chunk_set", "rc_decode_batch_chunk_set",
+            "rc_cost_table", "rc_chunk_set_costs", "rc_histogram_by_class")
+    old6 = not hasattr(L, cset[0])
+    if not old6:
+        L.rc_model_create_chunk_set.argtypes = [_P, _U32, _U32, _P, _P, _U32, ctypes.POINTER(_P)]
+        L.rc_encode_batch_chunk_set.argtypes = [_P, _P, _P, _P, _P, _U32, _P, _P, _P, _P]
+        L.rc_decode_batch_chunk_set.argtypes = [_P, _P, _P, _P, _P, _P, _P, _P, _U32, _P]
+        L.rc_cost_table.argtypes = [_P, _U32, _U32, _P]
+        L.rc_chunk_set_costs.argtypes = [_P, _P, _U32, _P, _U32, _P, _P, _P]
+        L.rc_histogram_by_class.argtypes = [_P, _P, _P, _U32, _U32, _P]
+        # host-only hooks (not in the header; tests/test_chunk_set.py): the constructor's
+        # validation, its plan (10 words), the grouping rule, and the device grouping itself
+        L.rc_chunk_set_check_.argtypes = [_U32, _U32, _P, _P, _U32]
+        L.rc_chunk_set_check_.restype = _I
+        L.rc_chunk_set_plan_.argtypes = [_U32, _U32, _P, _P, _U32, _P]
+        L.rc_chunk_set_plan_.restype = _I
+        L.rc_chunk_group_plan_.argtypes = [_P, _U32, _U32, _U32, _P, _P]
+        L.rc_chunk_group_plan_.restype = _I
+        L.rc_chunk_group_.argtypes = [_P, _P, _U32, _U32, _U32, _P, _P, _P]
+        L.rc_chunk_group_.restype = _I
+        L.rc_chunk_last_.argtypes = [_P, _P]
+        L.rc_chunk_last_.restype = _I
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit) \
+                and not (old6 and name in cset) \
                 and not (old2 and name in c2) and not (old3 and name in per) \
                 and not (old4 and name in cj) and not (old5 and name in lag):
             getattr(L, name).restype = _I

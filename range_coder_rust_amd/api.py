@@ -480,6 +480,27 @@ class StaticModelSet:
     __del__ = StaticModel.__del__
 
 
+class ChunkModelSet(StaticModelSet):
+    """rc_model_create_chunk_set: K static tables (rows) over one alphabet and one total_freq,
+    for the chunk-set batch calls, which take one row per CHUNK: chunk k is coded exactly as
+    encode_batch / decode_batch code it with StaticModel(row class_of[k]).
+
+    Construction, the checks (rc_chunk_set_check_: the static set's rules) and the attributes c,
+    cum, total, n_models, n_symbols and max_bits_per_symbol() are StaticModelSet's; the device
+    snapshot is another (per row what a StaticModel builds), so the two kinds do not mix."""
+
+    @property
+    def handle(self):
+        if self._handle is None:
+            h = ctypes.c_void_p()
+            N.check(self.ctx._lib.rc_model_create_chunk_set(
+                self.ctx.handle, self.n_models, self.n_symbols,
+                ctypes.c_void_p(self.c.ctypes.data), ctypes.c_void_p(self.cum.ctypes.data),
+                ctypes.c_uint32(self.total), ctypes.byref(h)), "rc_model_create_chunk_set")
+            self._handle = h
+        return self._handle
+
+
 class Order1ModelSet:
     """rc_model_create_order1_set: the K rows of a StaticModelSet plus a context map, for the
     order-1 batch calls, in which the previous symbol of the chunk picks the row: symbol 0 of
@@ -914,6 +935,86 @@ def decode_chunks_indexed(model_set, chunks, raise_on_error=True):
     idxs = [_u8_chunk(x) for _, x in chunks]
     return _decode_chunks(decode_batch_indexed, model_set, [c for c, _ in chunks],
                           [len(x) for x in idxs], idxs, raise_on_error)
+
+
+# ------------------------------------------------------------- batch API, a model per chunk
+def encode_batch_chunk_set(chunk_set, class_of, syms, sym_off, out, out_off, out_len=None,
+                           flags=None):
+    """rc_encode_batch_chunk_set on torch tensors (async on torch's current stream): encode_batch
+    with class_of uint8[n], the row of chunk_set (a ChunkModelSet) that codes chunk k.
+    Returns (out_len int64[n], flags int32[n]) device tensors."""
+    torch = _torch()
+    _check_syms(syms, "syms", False)
+    _check_dev(class_of, "class_of", (torch.uint8,))
+    _check_dev(out, "out", (torch.uint8,))
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    _check_dev(out_off, "out_off", (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    if out_off.numel() != n + 1:
+        raise ValueError("out_off must have n_chunks + 1 entries")
+    if class_of.numel() < n:
+        raise ValueError("class_of must hold one class per chunk")
+    if out_len is None:
+        out_len = torch.empty(max(n, 1), dtype=torch.int64, device=syms.device)
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=syms.device)
+    ctx = chunk_set.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_encode_batch_chunk_set(
+        ctx.handle, chunk_set.handle, _ptr(class_of), _ptr(syms), _ptr(sym_off), n, _ptr(out),
+        _ptr(out_off), _ptr(out_len), _ptr(flags)), "rc_encode_batch_chunk_set")
+    return out_len[:n], flags[:n]
+
+
+def decode_batch_chunk_set(chunk_set, class_of, code, code_off, code_len, syms_out, sym_off,
+                           flags=None):
+    """rc_decode_batch_chunk_set on torch tensors (async on torch's current stream): decode_batch
+    with class_of uint8[n], the row of chunk_set that codes chunk k.  Returns flags."""
+    torch = _torch()
+    _check_dev(code, "code", (torch.uint8,))
+    _check_dev(class_of, "class_of", (torch.uint8,))
+    _check_syms(syms_out, "syms_out", False)
+    for name, t in (("code_off", code_off), ("code_len", code_len), ("sym_off", sym_off)):
+        _check_dev(t, name, (torch.int64, torch.uint64))
+    n = sym_off.numel() - 1
+    if code_off.numel() < n or code_len.numel() < n:
+        raise ValueError("code_off/code_len need n_chunks entries")
+    if class_of.numel() < n:
+        raise ValueError("class_of must hold one class per chunk")
+    if flags is None:
+        flags = torch.empty(max(n, 1), dtype=torch.int32, device=code.device)
+    ctx = chunk_set.ctx
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_decode_batch_chunk_set(
+        ctx.handle, chunk_set.handle, _ptr(class_of), _ptr(code), _ptr(code_off), _ptr(code_len),
+        _ptr(syms_out), _ptr(sym_off), n, _ptr(flags)), "rc_decode_batch_chunk_set")
+    return flags[:n]
+
+
+def _class_tensor(chunk_set, class_of, n):
+    cls = np.ascontiguousarray(class_of, dtype=np.uint8).reshape(-1)
+    if len(cls) != n:
+        raise ValueError(f"{n} chunks, {len(cls)} classes")
+    torch = _torch()
+    return torch.from_numpy(cls if n else np.zeros(1, np.uint8)).to(
+        torch.device("cuda", chunk_set.ctx.device))
+
+
+def encode_chunks_chunk_set(chunk_set, class_of, chunks, raise_on_error=True):
+    """encode_chunks over a list of symbol chunks (bytes / uint8 arrays), chunk k against row
+    class_of[k] of a ChunkModelSet.  Returns a list of bytes."""
+    arrs = [_u8_chunk(c) for c in chunks]
+    cls_d = _class_tensor(chunk_set, class_of, len(arrs))
+    return _encode_chunks(lambda m, *a: encode_batch_chunk_set(m, cls_d, *a), chunk_set, arrs, None,
+                          raise_on_error)
+
+
+def decode_chunks_chunk_set(chunk_set, class_of, codes, counts, raise_on_error=True):
+    """decode_chunks against a ChunkModelSet: counts[k] symbols from codes[k] with row
+    class_of[k].  Returns a list of uint8 numpy arrays."""
+    cls_d = _class_tensor(chunk_set, class_of, len(codes))
+    return _decode_chunks(lambda m, *a: decode_batch_chunk_set(m, cls_d, *a), chunk_set, codes,
+                          counts, None, raise_on_error)
 
 
 # ------------------------------------------------- batch API, the previous symbol picks the model

@@ -1,6 +1,7 @@
 // rc_decode.inc — k_decode_static, the static-model decoder; included by rc_decode_pow2.hip and
 // rc_decode_magic.hip with RC_DEC_DIV set (see rc_static.h for the shared design notes).
 #include "rc_static.h"
+#include "rc_chunk_set.h"
 
 
 // ------------------------------------------------------------------------------------------
@@ -18,7 +19,15 @@ typedef __attribute__((address_space(3))) u32 l_u32;
 
 // RC_DEC_SHARED_ONLY (rc_indexed.hip): the per-lane machinery alone (code ring, dec_apply,
 // dec_fix, dec_rare), without k_decode_static and its launchers
+// RC_DEC_GROUPED (rc_decode_grouped_pow2.hip, rc_decode_grouped_magic.hip): the chunk sets'
+// grouped instantiations of the decoder body and their launcher, without k_decode_static
 #ifdef RC_DEC_SHARED_ONLY
+#elif defined(RC_DEC_GROUPED) && RC_DEC_DIV == 0
+#define RC_DEC_TU dec_grp_pow2
+RC_STAMP_DEFINE(dec_grp_pow2)
+#elif defined(RC_DEC_GROUPED)
+#define RC_DEC_TU dec_grp_magic
+RC_STAMP_DEFINE(dec_grp_magic)
 #elif RC_DEC_DIV == 0  // (scratch -DRC_STAMP builds: one stamp buffer per translation unit)
 #define RC_DEC_TU dec_pow2
 RC_STAMP_DEFINE(dec_pow2)
@@ -651,9 +660,20 @@ static __device__ __forceinline__ uint4 dec_phase16(D& d, const ModelArgs& m,
 #else
 #define RC_DEC_ATTR
 #endif
+// k_decode_static, and with RC_DEC_GROUPED its grouped twin k_decode_static_grouped (static chunk
+// sets, rc_chunk_set.h): the lane's chunk comes from g.order, and the workgroup stages the tables
+// of its class, row g.wg_row[blockIdx.x] of the set.  The preprocessor makes the difference, so
+// that k_decode_static compiles from the tokens it had before there were chunk sets.
+#ifdef RC_DEC_GROUPED
+#define RC_DEC_KERNEL k_decode_static_grouped
+#define RC_DEC_GRP_PARAM GroupArgs g,
+#else
+#define RC_DEC_KERNEL k_decode_static
+#define RC_DEC_GRP_PARAM
+#endif
 template <int DIV, int SM, int LUT, int WGS = WG, int LD = DEC_LD>
-__global__ __launch_bounds__(WGS) RC_DEC_ATTR void k_decode_static(
-    ModelArgs m, const uint8_t* __restrict__ code, const u64* __restrict__ code_off,
+__global__ __launch_bounds__(WGS) RC_DEC_ATTR void RC_DEC_KERNEL(
+    ModelArgs m, RC_DEC_GRP_PARAM const uint8_t* __restrict__ code, const u64* __restrict__ code_off,
     const u64* __restrict__ code_len, uint8_t* __restrict__ syms_out,
     const u64* __restrict__ sym_off, u32 n_chunks, u32* __restrict__ flags) {
   // small models always carry LUT 4's 8-B buckets (rc_model_create_static); the LUT 0 bucket
@@ -661,6 +681,15 @@ __global__ __launch_bounds__(WGS) RC_DEC_ATTR void k_decode_static(
   static_assert(!(SM && LUT == 0), "small models decode through LUT 3 or LUT 4");
   RC_STAMP_BEGIN();
   rc_set_prio(m);
+#ifdef RC_DEC_GROUPED
+  {  // a workgroup with no class leaves before staging
+    const u32 row = g.wg_row[blockIdx.x];
+    if (row == ~0u) return;
+    m.tab += (size_t)row * 256;
+    m.lut += (size_t)row * g.lut_stride;
+    if (LUT == 6) m.symof += (size_t)row * g.symof_stride;
+  }
+#endif
   // All LDS is dynamic, sized at launch (the WG's footprint sets how many WGs share a CU):
   // the LUT (lut_max + 1 entries) first, at LDS address 0, so a table read is a ds_read at the
   // hint's byte offset with no base add; then the (cum, c) table and the code rings.
@@ -700,8 +729,13 @@ __global__ __launch_bounds__(WGS) RC_DEC_ATTR void k_decode_static(
   }
   for (u32 j = tid; j < lut_n; j += WGS) s_lut[j] = lut_src[j];
   __syncthreads();
+#ifdef RC_DEC_GROUPED
+  const u32 k = g.order[blockIdx.x * WGS + tid];
+  if (k == ~0u) return;  // a dead lane
+#else
   const u32 k = blockIdx.x * WGS + tid;
   if (k >= n_chunks) return;
+#endif
   // f32 rounding toward zero from here on (MODE.FP_ROUND f32 bits = 3), for hint_floor.  The
   // other float operations only form hints and the carried hint scale, which the exact
   // verification backs, so their rounding direction does not matter.
@@ -863,6 +897,61 @@ bool symof_candidate(const RcKnobs& k, const ModelArgs& a, int sm) {
 }
 }  // namespace
 
+#ifdef RC_DEC_GROUPED
+// The variant a chunk set's rows decode through when the direct q-to-symbol table is not taken
+// (no row is flat, none carries pair tables: DESIGN.md §9.20), and its lanes per workgroup
+static u32 rc_chunk_decode_class_(const ModelArgs& a, int* lut) {
+  *lut = a.direct == 2 ? 2 : a.direct ? 1 : 4;
+  return !a.direct && SMB_WG(a.lut_max + 1) == 512 ? 512u : (u32)WG;
+}
+
+#if RC_DEC_DIV == 0
+u32 rc_chunk_decode_class(const ModelArgs& a, int* lut) { return rc_chunk_decode_class_(a, lut); }
+hipError_t rc_chunk_decode_launch_pow2(
+#else
+hipError_t rc_chunk_decode_launch_magic(
+#endif
+    hipStream_t stream, const RcKnobs& k, const ModelArgs& a_in, const ChunkSetArgs& cs,
+    GroupScratch& sc, const uint8_t* class_of, const uint8_t* code, const u64* code_off,
+    const u64* code_len, uint8_t* syms_out, const u64* sym_off, u32 n_chunks, u32* flags) {
+  ModelArgs a = a_in;
+  // k_decode_static's launch (below) at the padded workgroup count, after the grouping for the
+  // variant's workgroup size
+  auto go = [&](auto kern, u32 wgs, size_t lds, PrioPolicy dflt, u32 lut_of) {
+    GroupArgs g{nullptr, nullptr, cs.lut_stride, cs.symof_stride};
+    const hipError_t e =
+        rc_chunk_group_launch(stream, sc, class_of, n_chunks, cs.k, wgs, flags, nullptr, &g);
+    if (e != hipSuccess) return e;
+    const dim3 grid(rc_group_grid(n_chunks, cs.k, wgs)), block(wgs);
+    rc_prio_policy(a, dflt, grid.x,
+                   rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)wgs, lds), k);
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, a, g, code, code_off, code_len, syms_out,
+                       sym_off, n_chunks, flags);
+    const hipError_t le = hipGetLastError();
+    const hipError_t de = rc_chunk_group_done(stream, sc, wgs, lut_of, grid.x);
+    return le != hipSuccess ? le : de;
+  };
+  // (RC_DEC_PAIR=512 / 1024 finds no pair table here and falls through to LUT 4)
+  if (symof_candidate(k, a, 1)) {
+    const auto kern = k_decode_static_grouped<RC_DEC_DIV, 1, 6, SYMOF_WG>;
+    const size_t lds = rc_static_decode_lds(a, 6, SYMOF_WG);
+    const hipError_t e = set_allow_lds(reinterpret_cast<const void*>(kern));
+    if (e != hipSuccess) return e;
+    if (symof_launch(k, a, rc_group_grid(n_chunks, cs.k, SYMOF_WG) * SYMOF_WG,
+                     rc_resident_wgs(reinterpret_cast<const void*>(kern), (int)SYMOF_WG, lds)))
+      return go(kern, SYMOF_WG, lds, kPrioDecoder1024, 6);
+  }
+  int lut = 0;
+  const u32 wgs = rc_chunk_decode_class_(a, &lut);
+  const size_t lds = rc_static_decode_lds(a, 0, wgs);
+  if (wgs == 512)
+    return go(k_decode_static_grouped<RC_DEC_DIV, 1, 4, 512>, 512, lds, kPrioDecoder512, 4);
+  if (lut == 2) return go(k_decode_static_grouped<RC_DEC_DIV, 1, 2>, WG, lds, kPrioDecoder, 2);
+  if (lut == 1) return go(k_decode_static_grouped<RC_DEC_DIV, 1, 1>, WG, lds, kPrioDecoder, 1);
+  return go(k_decode_static_grouped<RC_DEC_DIV, 1, 4>, WG, lds, kPrioDecoder, 4);
+}
+#else  // RC_DEC_GROUPED
+
 #if RC_DEC_DIV == 0
 hipError_t rc_static_decode_launch_pow2(
 #else
@@ -951,4 +1040,5 @@ size_t rc_static_decode_lds(const ModelArgs& a, int lut, u32 wgs) {
   return head + rings + extra;
 }
 #endif
+#endif  // RC_DEC_GROUPED
 #endif  // RC_DEC_SHARED_ONLY

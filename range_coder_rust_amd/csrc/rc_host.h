@@ -9,6 +9,7 @@
 #include "rc_indexed.h"
 #include "rc_order1.h"
 #include "rc_wide.h"
+#include "rc_chunk_set.h"
 
 struct rc_ctx {
   int device;
@@ -20,6 +21,7 @@ struct rc_ctx {
   // 2 lane) and the device's CU count for the rule (0: not asked yet)
   u32 rows_decoder = 0;
   u32 n_cus = 0;
+  GroupScratch group;  // the chunk-set calls' grouping scratch (rc_chunk_set.h), grown on demand
 };
 
 enum {
@@ -27,7 +29,8 @@ enum {
   RC_KIND_ADAPTIVE = 1,
   RC_KIND_SET = 2,
   RC_KIND_WIDE = 3,
-  RC_KIND_ORDER1 = 4
+  RC_KIND_ORDER1 = 4,
+  RC_KIND_CHUNK_SET = 5
 };
 
 struct rc_model {
@@ -38,6 +41,7 @@ struct rc_model {
   SetPlan plan;
   WideArgs wide;
   WidePlan wplan;
+  ChunkSetArgs cset;  // kind 5, a static chunk set (rc_chunk_set.h): `args` is row 0's
   O1Args o1;  // kind 4 (o1.period: 1, 2, 4 or 8)
   u32 o1_lag;  // kind 4: 1, 2, 4 or 8 (rc_order1.h: no field of the kernels' O1Args)
   int device;

@@ -362,6 +362,7 @@ rc_status rc_ctx_destroy(rc_ctx* ctx) {
   (void)hipStreamSynchronize(ctx->own);
   (void)hipStreamSynchronize(ctx->cur);
   (void)hipFree(ctx->inv);
+  rc_chunk_group_release(ctx->group);
   (void)hipStreamDestroy(ctx->own);
   delete ctx;
   return RC_OK;
@@ -805,6 +806,135 @@ rc_status rc_decode_batch_indexed(rc_ctx* ctx, const rc_model* set, const uint8_
                                                   set->plan, code, code_off, code_len, idx,
                                                   syms_out, sym_off, n_chunks, flags);
                     });
+}
+
+// ---- static chunk sets (rc_chunk_set.h; kernels in rc_chunk_set.hip, rc_decode_grouped_*.hip) ----
+
+// The rows of a checked chunk set as the static coders' tables: per row what static_tables builds
+// for it, less what a chunk set does not carry (no row is flat and none has pair tables: DESIGN.md
+// §9.20).  With one total the class, the constants and the table sizes are those of the total, so
+// the rows' ModelArgs differ in the table pointers alone: *a is row 0's (pointers null), and the
+// segments hold the rows back to back.
+struct ChunkSetTables {
+  ModelArgs a;
+  ChunkSetArgs cs;
+  std::vector<uint2> tab;
+  std::vector<u32> lut;
+  std::vector<uint8_t> symof;
+};
+static rc_status chunk_set_tables(u32 n_models, u32 n_symbols, const u32* c, const u32* cum,
+                                  u32 total, ChunkSetTables* t) {
+  bool complete = true;
+  for (u32 j = 0; j < n_models; ++j) {
+    StaticTables st;
+    const rc_status built = static_tables(n_symbols, c + (size_t)j * n_symbols,
+                                          cum + (size_t)j * n_symbols, total, &st);
+    if (built != RC_OK) return built;
+    if (j == 0) {
+      t->a = st.a;
+      t->a.flat = 0;
+      t->cs.lut_stride = (u32)st.lut.size();
+      t->cs.symof_stride = (u32)st.symof.size();
+    }
+    // (unreachable: the sizes follow from the total)
+    if (st.tab.size() != 256 || st.lut.size() != t->cs.lut_stride ||
+        st.symof.size() != t->cs.symof_stride || (st.lut.size() & 3) || (st.symof.size() & 15))
+      return RC_E_BAD_MODEL;
+    t->tab.insert(t->tab.end(), st.tab.begin(), st.tab.end());
+    t->lut.insert(t->lut.end(), st.lut.begin(), st.lut.end());
+    t->symof.insert(t->symof.end(), st.symof.begin(), st.symof.end());
+    complete = complete && st.complete;
+  }
+  t->cs.k = n_models;
+  t->cs.smv = complete ? 2u : 1u;
+  return RC_OK;
+}
+
+// Internal test hooks (not in include/range_coder.h; host only, no device needed).
+// rc_chunk_set_check_: rc_model_create_chunk_set's validation of its tables (the static set's).
+rc_status rc_chunk_set_check_(uint32_t n_models, uint32_t n_symbols, const uint32_t* c_freq,
+                              const uint32_t* cum_freq, uint32_t total_freq) {
+  return set_check(n_models, n_symbols, c_freq, cum_freq, total_freq);
+}
+// rc_chunk_set_plan_: what the launchers use for the set, out[10] = {the encoder variant (2: every
+// row complete, else 1), the decoder's LUT when the direct q-to-symbol table is not taken (2, 1
+// or 4), its lanes per workgroup, has_symof (LUT 6 can be taken), div (0 DIV_POW2, 1 DIV_MAGIC),
+// tab stride (bytes between two rows), lut stride (bytes), symof stride (bytes), has_pair (0),
+// flat (0)}.
+rc_status rc_chunk_set_plan_(uint32_t n_models, uint32_t n_symbols, const uint32_t* c_freq,
+                             const uint32_t* cum_freq, uint32_t total_freq, uint32_t* out) {
+  if (!out) return RC_E_ARG;
+  const rc_status ok = set_check(n_models, n_symbols, c_freq, cum_freq, total_freq);
+  if (ok != RC_OK) return ok;
+  ChunkSetTables t;
+  const rc_status built = chunk_set_tables(n_models, n_symbols, c_freq, cum_freq, total_freq, &t);
+  if (built != RC_OK) return built;
+  int lut = 0;
+  const u32 lanes = rc_chunk_decode_class(t.a, &lut);
+  const u32 v[10] = {t.cs.smv, (u32)lut, lanes, (u32)(t.cs.symof_stride != 0),
+                     (u32)div_of(total_freq), 256u * (u32)sizeof(uint2), 4u * t.cs.lut_stride,
+                     t.cs.symof_stride, t.a.pair ? 1u : 0u, t.a.flat};
+  memcpy(out, v, sizeof v);
+  return RC_OK;
+}
+
+rc_status rc_model_create_chunk_set(rc_ctx* ctx, uint32_t n_models, uint32_t n_symbols,
+                                    const uint32_t* c_freq, const uint32_t* cum_freq,
+                                    uint32_t total_freq, rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
+  *out = nullptr;
+  const rc_status ok = set_check(n_models, n_symbols, c_freq, cum_freq, total_freq);
+  if (ok != RC_OK) return ok;
+  ChunkSetTables t;
+  const rc_status built = chunk_set_tables(n_models, n_symbols, c_freq, cum_freq, total_freq, &t);
+  if (built != RC_OK) return built;
+  const size_t tab_bytes = t.tab.size() * sizeof(uint2), lut_bytes = t.lut.size() * sizeof(u32);
+  rc_model* mm = nullptr;
+  char* d = nullptr;
+  const rc_status up = model_upload(
+      ctx, RC_KIND_CHUNK_SET, total_freq,
+      {{t.tab.data(), tab_bytes}, {t.lut.data(), lut_bytes}, {t.symof.data(), t.symof.size()}},
+      &mm, &d);
+  if (up != RC_OK) return up;
+  t.a.tab = (const uint2*)d;
+  t.a.lut = (const u32*)(d + tab_bytes);
+  t.a.pair = nullptr;
+  t.a.symof = t.symof.empty() ? nullptr : (const uint8_t*)(d + tab_bytes + lut_bytes);
+  mm->args = t.a;
+  mm->cset = t.cs;
+  *out = mm;
+  return RC_OK;
+}
+
+rc_status rc_encode_batch_chunk_set(rc_ctx* ctx, const rc_model* set, const uint8_t* class_of,
+                                    const uint8_t* syms, const uint64_t* sym_off,
+                                    uint32_t n_chunks, uint8_t* out, const uint64_t* out_off,
+                                    uint64_t* out_len, uint32_t* flags) {
+  return batch_call(ctx, set, 1u << RC_KIND_CHUNK_SET, true, n_chunks,
+                    class_of && syms && sym_off && out && out_off && out_len && flags,
+                    "chunk-set encode launch", [&] {
+                      return rc_chunk_encode_launch(ctx->cur, ctx->knobs, set->args, set->div,
+                                                    set->cset, ctx->group, class_of, syms, sym_off,
+                                                    n_chunks, out, out_off, out_len, flags);
+                    });
+}
+
+rc_status rc_decode_batch_chunk_set(rc_ctx* ctx, const rc_model* set, const uint8_t* class_of,
+                                    const uint8_t* code, const uint64_t* code_off,
+                                    const uint64_t* code_len, uint8_t* syms_out,
+                                    const uint64_t* sym_off, uint32_t n_chunks, uint32_t* flags) {
+  return batch_call(
+      ctx, set, 1u << RC_KIND_CHUNK_SET, true, n_chunks,
+      class_of && code && code_off && code_len && syms_out && sym_off && flags,
+      "chunk-set decode launch", [&] {
+        return set->div == DIV_POW2
+                   ? rc_chunk_decode_launch_pow2(ctx->cur, ctx->knobs, set->args, set->cset,
+                                                 ctx->group, class_of, code, code_off, code_len,
+                                                 syms_out, sym_off, n_chunks, flags)
+                   : rc_chunk_decode_launch_magic(ctx->cur, ctx->knobs, set->args, set->cset,
+                                                  ctx->group, class_of, code, code_off, code_len,
+                                                  syms_out, sym_off, n_chunks, flags);
+      });
 }
 
 // ---- order-1 sets (rc_order1.h; kernels in rc_order1.hip) ----

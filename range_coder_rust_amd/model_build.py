@@ -28,13 +28,19 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
   build_wide_model(syms, sym_off, n)         those counts -> WideStaticModel, in one call
   ideal_bits_wide(model, syms, sym_off)      rc_ideal_bits_wide: per-chunk ideal bits of a wide
                                   model, straight from the symbols (HIP)
+  cost_table(c, total)            rc_cost_table: a row's integer costs, 2^-16 bit units (host)
+  chunk_set_costs(chunk_hist, cost_rows)     rc_chunk_set_costs: every chunk's cost under every
+                                  row, and its cheapest row (HIP)
+  histogram_by_class(chunk_hist, class_of, K)  rc_histogram_by_class: rc_histogram's rows summed
+                                  per class (HIP)
+  fit_chunk_set(syms, sym_off, K) histograms -> K classes by cost -> (ChunkModelSet, class_of)
 """
 import ctypes
 
 import numpy as np
 
 from . import _native as N
-from .api import (Order1ModelSet, StaticModel, WideStaticModel, _check_dev, _ptr, _sym16, _torch,
+from .api import (ChunkModelSet, Order1ModelSet, StaticModel, WideStaticModel, _check_dev, _ptr, _sym16, _torch,
                   default_context)
 
 
@@ -471,3 +477,129 @@ def ideal_bits(model, chunk_hist):
                                    model.total, _ptr(chunk_hist), n, _ptr(bits)),
             "rc_ideal_bits")
     return bits[:n]
+
+
+# ---------------------------------------------------------------------- static chunk sets
+def cost_table(c, total):
+    """rc_cost_table (host): uint32[len(c)], round(65536 log2(total / c)) per symbol and
+    0xFFFFFFFF where c == 0."""
+    cc = np.ascontiguousarray(c, dtype=np.uint32)
+    out = np.zeros(max(len(cc), 1), np.uint32)
+    N.check(N.load().rc_cost_table(ctypes.c_void_p(cc.ctypes.data), len(cc), int(total),
+                                   ctypes.c_void_p(out.ctypes.data)), "rc_cost_table")
+    return out[:len(cc)]
+
+
+def chunk_set_costs(chunk_hist, cost_rows, all_costs=False, ctx=None):
+    """rc_chunk_set_costs on torch tensors (torch's current stream): chunk_hist int32[n, 256]
+    (histogram's per-chunk rows), cost_rows [K, <= 256] uint32 on the host (cost_table's; the
+    entries past a row's alphabet count as 0xFFFFFFFF).  Returns (best_row uint8[n], best_cost
+    int64[n], costs int64[n, K] or None); a cost of -1 is UINT64_MAX, a chunk the row cannot
+    code."""
+    torch = _torch()
+    _check_dev(chunk_hist, "chunk_hist", (torch.int32,))
+    rows = np.atleast_2d(np.asarray(cost_rows, dtype=np.uint32))
+    K = rows.shape[0]
+    if not 1 <= K <= N.MAX_SET_MODELS or rows.shape[1] > 256 or rows.shape[1] < 1:
+        raise ValueError(f"cost_rows must be [1..{N.MAX_SET_MODELS}, 1..256]")
+    tab = np.full((K, 256), 0xFFFFFFFF, np.uint32)
+    tab[:, :rows.shape[1]] = rows
+    if chunk_hist.dim() != 2 or chunk_hist.shape[1] != 256 or not chunk_hist.is_contiguous():
+        raise ValueError("chunk_hist must be a contiguous [n, 256]")
+    n = chunk_hist.shape[0]
+    dev = chunk_hist.device
+    ctx = ctx or default_context(dev.index)
+    best_row = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    best_cost = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    costs = torch.empty((max(n, 1), K), dtype=torch.int64, device=dev) if all_costs else None
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_chunk_set_costs(ctx.handle, _ptr(chunk_hist), n,
+                                        ctypes.c_void_p(tab.ctypes.data), K, _ptr(best_row),
+                                        _ptr(best_cost), _ptr(costs)), "rc_chunk_set_costs")
+    return best_row[:n], best_cost[:n], (costs[:n] if all_costs else None)
+
+
+def histogram_by_class(chunk_hist, class_of, n_models, class_hist=None, ctx=None):
+    """rc_histogram_by_class on torch tensors (async, torch's current stream): int64[K, 256], row
+    c = the sum of the chunk_hist rows of the chunks with class_of[k] == c (a class id >= K is
+    skipped).  class_hist: the sums are added into it."""
+    torch = _torch()
+    _check_dev(chunk_hist, "chunk_hist", (torch.int32,))
+    _check_dev(class_of, "class_of", (torch.uint8,))
+    K = int(n_models)
+    if not 1 <= K <= N.MAX_SET_MODELS:
+        raise ValueError(f"n_models must be 1..{N.MAX_SET_MODELS}")
+    if chunk_hist.dim() != 2 or chunk_hist.shape[1] != 256 or not chunk_hist.is_contiguous():
+        raise ValueError("chunk_hist must be a contiguous [n, 256]")
+    n = chunk_hist.shape[0]
+    if class_of.numel() < n:
+        raise ValueError("class_of must hold one class per chunk")
+    if class_hist is None:
+        class_hist = torch.zeros((K, 256), dtype=torch.int64, device=chunk_hist.device)
+    else:
+        _check_dev(class_hist, "class_hist", (torch.int64, torch.uint64))
+        if tuple(class_hist.shape) != (K, 256):
+            raise ValueError(f"class_hist must be [{K}, 256]")
+    ctx = ctx or default_context(chunk_hist.device.index)
+    ctx.bind_stream()
+    N.check(ctx._lib.rc_histogram_by_class(ctx.handle, _ptr(chunk_hist), _ptr(class_of), n, K,
+                                           _ptr(class_hist)), "rc_histogram_by_class")
+    return class_hist
+
+
+def fit_chunk_set(syms, sym_off, n_models=8, target_total=1 << 16, iters=8, ctx=None):
+    """A ChunkModelSet of at most n_models rows fitted to the batch, and the chunks' classes
+    (uint8[n] device tensor): the rule of tests/chunk_fit_ref.py.  Row 0 starts
+    as the pooled table; the dearest chunk under its best row seeds each further row; then at most
+    `iters` rounds of reassigning the chunks and re-estimating the rows, until the assignment
+    repeats.  Rows that end without a member are dropped.  The histogram, the costs, the sums by
+    class (all HIP) and rc_quantize_counts do the work; torch is glue."""
+    torch = _torch()
+    K = int(n_models)
+    if not 1 <= K <= N.MAX_SET_MODELS:
+        raise ValueError(f"n_models must be 1..{N.MAX_SET_MODELS}")
+    ctx = ctx or default_context(syms.device.index)
+    hist, ch = histogram(syms, sym_off, per_chunk=True, ctx=ctx)
+    n = ch.shape[0]
+
+    def quant(counts):
+        return quantize_counts(np.asarray(counts, dtype=np.uint64), target_total, True)[0]
+
+    rows = [quant(hist.cpu().numpy())]
+
+    def assign():
+        best, cost, _ = chunk_set_costs(ch, [cost_table(r, target_total) for r in rows], ctx=ctx)
+        return best, cost
+
+    def reestimate(cls):
+        sums = histogram_by_class(ch, cls, len(rows), ctx=ctx).cpu().numpy()
+        for r in range(len(rows)):
+            if sums[r].any():
+                rows[r] = quant(sums[r])
+
+    cls = torch.zeros(max(n, 1), dtype=torch.uint8, device=syms.device)[:n]
+    while len(rows) < K and n:
+        cls, cost = assign()
+        top = cost.max()
+        if int(top) == 0:
+            break
+        seed = int(torch.nonzero(cost == top)[0])  # (the lowest chunk id among the dearest)
+        rows.append(quant(ch[seed].cpu().numpy()))
+        cls, _ = assign()
+        reestimate(cls)
+    for _ in range(int(iters)):
+        new, _ = assign()
+        same = torch.equal(new, cls)
+        cls = new
+        if same:
+            break
+        reestimate(cls)
+    if n:
+        cls, _ = assign()
+    members = torch.bincount(cls.to(torch.int64), minlength=len(rows)).cpu().numpy()
+    used = [r for r in range(len(rows)) if members[r]] or [0]
+    remap = np.zeros(len(rows), np.uint8)
+    remap[used] = np.arange(len(used), dtype=np.uint8)
+    cls = torch.from_numpy(remap).to(syms.device)[cls.to(torch.int64)]
+    c = np.stack([rows[r] for r in used])
+    return ChunkModelSet(c, None, int(target_total), ctx=ctx), cls

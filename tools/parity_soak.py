@@ -15,7 +15,7 @@ kernels specialise on:
           rare symbols of skewed models exercise both renormalisation loops), or runs of one
           symbol
   chunks  1 .. 3000 chunks, lengths 0 .. 70000 with ragged mixes (0, 1, 7, 4095, 65536, ...)
-A quarter of the iterations instead draw one of:
+A third of the iterations instead draw one of:
   adaptive    the build-defined adaptive model (rc_model_create_adaptive) with random valid
               parameters, 1 .. 300 ragged chunks, against orc_encode_adaptive chunk by chunk
   stream-enc  1 .. 200 resumable streams of random (c, cum, total) triples, valid or not (the
@@ -25,10 +25,15 @@ A quarter of the iterations instead draw one of:
   stream-dec  1 .. 200 streams, valid or garbage code, decoded under one random table (zero
               frequencies, inconsistent cum) by rc_stream_decode, against orc_stream_decode:
               symbols, state and flags
+  chunk-set   a static chunk set (rc_model_create_chunk_set) of 1 .. 64 random rows over one total
+              in [256, 2^16], 1 .. 1500 ragged chunks with a random class each (now and then one
+              that names no row: RC_F_BAD_MODEL), against the oracle chunk by chunk with the
+              chunk's row, and the round trip
 Prints a progress line per iteration and one JSON summary line; exits 1 at the first mismatch
 (after printing what differed).  The oracle is the checker here, never the thing measured.
 
-Usage (GPU box): python3 tools/parity_soak.py [seconds] [seed]
+Usage (GPU box): python3 tools/parity_soak.py [seconds] [seed] [draw]
+(draw: only this one of adaptive, stream-enc, stream-dec, chunk-set)
 """
 import json
 import math
@@ -263,9 +268,69 @@ def stream_dec_iteration(rng):
             ns, ns * m, int(clen.sum()), bad)
 
 
+def chunk_set_iteration(rng):
+    K = int(rng.choice([1, 2, 3, 8, 64, int(rng.integers(1, 65))]))
+    total = int(rng.choice([256, 512, 513, 2048, 2049, 65535, 65536,
+                            int(rng.integers(256, 65537))]))
+    rows = []
+    for _ in range(K):
+        p = rng.random(256) ** 3 + 1e-3
+        if total > 256 and rng.random() < 0.5:  # zero frequencies (never drawn in the data)
+            p[rng.random(256) < 0.3] = 0.0
+            p[int(rng.integers(0, 256))] = 1.0
+        rows.append(quantise(p, total, rng))
+    cs = rc.ChunkModelSet(np.stack(rows), None, total)
+    n = int(rng.choice([1, 2, 255, 256, 257, 1024, int(rng.integers(1, 1501))]))
+    class_of = rng.integers(0, K, n).astype(np.uint8)
+    if rng.random() < 0.3:
+        class_of[rng.random(n) < 0.02] = int(rng.integers(K, 256))
+    lens = rng.choice([0, 1, 15, 16, 17, 63, 64, 65, 300, 4097], n).astype(np.int64)
+    chunks = []
+    for k in range(n):
+        live = np.flatnonzero(rows[class_of[k] if class_of[k] < K else 0])
+        chunks.append(live[rng.integers(0, len(live), int(lens[k]))].astype(np.uint8))
+    data = np.concatenate(chunks + [np.zeros(1, np.uint8)])
+    sym_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    caps = np.array([rc.slot_capacity(int(L), cs.max_bits_per_symbol() + 0.5, slack=1.05)
+                     for L in lens], np.int64)
+    out_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    d_cls = torch.from_numpy(class_of).cuda()
+    d_syms, d_soff = torch.from_numpy(data).cuda(), torch.from_numpy(sym_off).cuda()
+    d_out = torch.zeros(int(out_off[-1]) + 16, dtype=torch.uint8, device="cuda")
+    ol, fe = rc.encode_batch_chunk_set(cs, d_cls, d_syms, d_soff, d_out,
+                                       torch.from_numpy(out_off).cuda())
+    dec = torch.zeros(int(sym_off[-1]) + 16, dtype=torch.uint8, device="cuda")
+    fd = rc.decode_batch_chunk_set(cs, d_cls, d_out, torch.from_numpy(out_off[:-1].copy()).cuda(),
+                                   ol, dec, d_soff)
+    torch.cuda.synchronize()
+    g_out, g_len, g_fe, g_fd = (t.cpu().numpy() for t in (d_out, ol, fe, fd))
+    g_dec = dec.cpu().numpy()
+    bad = []
+    for k in range(n):
+        a = int(out_off[k])
+        if class_of[k] >= K:
+            if (int(g_fe[k]), int(g_len[k]), int(g_fd[k])) != (64, 0, 64):
+                bad.append(f"chunk-set chunk {k}: class {class_of[k]} of {K} not refused")
+                break
+            continue
+        r = int(class_of[k])
+        f, want, L = cpu.encode(cs.c[r], cs.cum[r], total, chunks[k])
+        if f != int(g_fe[k]) or L != int(g_len[k]) or bytes(g_out[a:a + L]) != want:
+            bad.append(f"chunk-set encode of chunk {k} (row {r})")
+            break
+        if g_fd[k] != 0 or not np.array_equal(g_dec[sym_off[k]:sym_off[k + 1]], chunks[k]):
+            bad.append(f"chunk-set decode of chunk {k} (row {r})")
+            break
+    cs.close()
+    return (f"chunk-set K={K} total={total} chunks={n}", n, int(lens.sum()), int(g_len.sum()), bad)
+
+
 def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 20260518
+    only = {"adaptive": adaptive_iteration, "stream-enc": stream_enc_iteration,
+            "stream-dec": stream_dec_iteration,
+            "chunk-set": chunk_set_iteration}[sys.argv[3]] if len(sys.argv) > 3 else None
     rng = np.random.default_rng(seed)
     rc.default_context(0)
     t_end = time.time() + budget
@@ -273,9 +338,10 @@ def main():
     kinds = {}
     while time.time() < t_end:
         other = rng.random()
-        if other < 0.25:
-            fn = (adaptive_iteration if other < 0.1 else
-                  stream_enc_iteration if other < 0.175 else stream_dec_iteration)
+        if other < 0.35 or only:
+            fn = only or (adaptive_iteration if other < 0.1 else
+                          stream_enc_iteration if other < 0.175 else
+                          stream_dec_iteration if other < 0.25 else chunk_set_iteration)
             name, n, nsym, nbytes, bad = fn(rng)
             it += 1
             chunks += n
