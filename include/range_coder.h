@@ -406,7 +406,8 @@ rc_status rc_decode_batch_order1(rc_ctx* ctx, const rc_model* o1, const uint8_t*
  * total is bounded for the same reason as for sets: at most 3 bytes settle per symbol, so the
  * margins of both kernels' rings and RC_MAX_CHUNK_SYMBOLS hold unchanged.  The cap of 4096 is
  * where the table still sits in a CU's local memory beside at least 768 chunks' rings in both
- * directions; larger alphabets need tables outside it and are a later change.
+ * directions; larger alphabets, up to all 2^16 symbols, are coded by the
+ * wide16 models below, whose tables stay in device memory.
  *
  * Symbol buffers hold 16-bit unsigned symbols in host byte order and sym_off counts symbols,
  * not bytes.  They are declared void pointers; a symbol pointer that is not 2-byte aligned is
@@ -441,6 +442,46 @@ rc_status rc_decode_batch_wide(rc_ctx* ctx, const rc_model* wide, const uint8_t*
                                const uint64_t* code_off_dev, const uint64_t* code_len_dev,
                                void* syms16_out_dev, const uint64_t* sym_off_dev,
                                uint32_t n_chunks, uint32_t* flags_dev);
+
+/* ---- wide16 static models: the full 16-bit alphabet, tables in device memory ----
+ * A wide16 static model is one static table over up to RC_MAX_WIDE16_SYMBOLS (2^16) symbols, so
+ * bf16 / fp16 bit patterns, int16 samples and 16-bit indices are coded as they are.  The wide16
+ * batch calls have the wide calls' signatures and contract: symbol i of chunk k is coded exactly
+ * as encoder.encode(&table, sym[i]) and decoded exactly as decoder.decode(&table) with
+ * FreqTable::find_index over the table (its choice of n_symbols-1 when rfreq >= total and its
+ * choice among equal cum values included); bytes, lengths and flags are bit-identical to the
+ * reference arithmetic, and for n_symbols <= RC_MAX_WIDE_SYMBOLS to the wide calls'.
+ *
+ * Accepted when 1 <= n_symbols <= RC_MAX_WIDE16_SYMBOLS, 256 <= total_freq <= 65536 (a power of
+ * two or not) and the table passes rc_model_create_static's checks; anything else is
+ * RC_E_BAD_MODEL.  Zero-frequency symbols are allowed (an alphabet of 2^16 symbols with a total
+ * below 2^16 needs them).  The total stays in the small-model regime for the wide models'
+ * reason; totals above 2^16 are not supported.  The tables (at most 512 KiB of encoder entries,
+ * 128 KiB of q-to-symbol halfwords and a cum row) are built by the constructor in device memory
+ * and read through the L2; the decoder's workgroups stage the halfwords in a CU's local memory
+ * beside their rings.
+ *
+ * Symbol buffers, sym_off, the alignment rule, the flags (RC_F_BAD_SYMBOL for a value >=
+ * n_symbols; at n_symbols = 65536 no 16-bit value is one), the RC_F_CAPACITY length rule,
+ * RC_F_TOO_LONG, first-error-wins and the over-read and touch rules are the wide calls'.
+ *
+ * A wide16 model is its own kind of rc_model: the wide16 calls take nothing else (RC_E_ARG), and
+ * every other entry point that takes a model returns RC_E_ARG for a wide16 model (containers,
+ * sets, order-1 and host-memory helpers over wide16 models are not provided).  Destroy it with
+ * rc_model_destroy.                                                                           */
+#define RC_MAX_WIDE16_SYMBOLS 65536u
+rc_status rc_model_create_static_wide16(rc_ctx* ctx, uint32_t n_symbols,
+                                        const uint32_t* c_freq_host,
+                                        const uint32_t* cum_freq_host, uint32_t total_freq,
+                                        rc_model** out);
+rc_status rc_encode_batch_wide16(rc_ctx* ctx, const rc_model* wide16, const void* syms16_dev,
+                                 const uint64_t* sym_off_dev, uint32_t n_chunks,
+                                 uint8_t* out_dev, const uint64_t* out_off_dev,
+                                 uint64_t* out_len_dev, uint32_t* flags_dev);
+rc_status rc_decode_batch_wide16(rc_ctx* ctx, const rc_model* wide16, const uint8_t* code_dev,
+                                 const uint64_t* code_off_dev, const uint64_t* code_len_dev,
+                                 void* syms16_out_dev, const uint64_t* sym_off_dev,
+                                 uint32_t n_chunks, uint32_t* flags_dev);
 
 /* ---- synchronous host-memory helpers (stage through device memory, wait for completion;
  *      returns RC_E_CHUNK when any chunk is flagged — flags are still filled in).  Their
@@ -761,6 +802,14 @@ rc_status rc_quantize_counts(const uint64_t* counts_host, uint32_t n_symbols,
 rc_status rc_quantize_counts_wide(const uint64_t* counts_host, uint32_t n_symbols,
                                   uint64_t target_total, uint32_t qflags, uint32_t* c_out_host,
                                   uint32_t* cum_out_host, uint32_t* total_out_host);
+/* The same rule for the alphabets of wide16 static models: n_symbols <= RC_MAX_WIDE16_SYMBOLS.
+ * RC_Q_ALL_SYMBOLS with n_symbols above a nonzero target_total is RC_E_ARG (no table of that
+ * total keeps every symbol encodable).  The 16-bit histogram comes from
+ * rc_histogram_pairs_periodic(period 2) over the symbols' bytes.          */
+rc_status rc_quantize_counts_wide16(const uint64_t* counts_host, uint32_t n_symbols,
+                                    uint64_t target_total, uint32_t qflags,
+                                    uint32_t* c_out_host, uint32_t* cum_out_host,
+                                    uint32_t* total_out_host);
 
 /* Batched PModel::ideal_code_length (pmodel.rs:14-40): bits_dev[k] = sum over symbols s of
  * chunk k of log2(total / c[s]) = sum_i hist[k][i] * (ln total - ln c_i) / ln 2, in f64,

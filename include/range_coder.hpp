@@ -716,6 +716,92 @@ class WideModel {
   std::vector<uint32_t> c_, cum_;
   uint32_t total_ = 0;
 };
+
+// A wide16 static model (rc_model_create_static_wide16): WideModel's interface over an alphabet of
+// up to RC_MAX_WIDE16_SYMBOLS (2^16) 16-bit symbols, its tables in device memory.  For an
+// alphabet WideModel accepts too, both give the same bytes.
+class Wide16Model {
+ public:
+  Wide16Model(Context& ctx, const PModel& pm) : ctx_(&ctx) {
+    const uint32_t n = (uint32_t)pm.alphabet_count();
+    for (uint32_t i = 0; i < n; ++i) {
+      c_.push_back(pm.c_freq(i));
+      cum_.push_back(pm.cum_freq(i));
+    }
+    total_ = pm.total_freq();
+    create();
+  }
+  Wide16Model(Context& ctx, const std::vector<uint32_t>& c, const std::vector<uint32_t>& cum,
+              uint32_t total)
+      : ctx_(&ctx), c_(c), cum_(cum), total_(total) {
+    if (c.size() != cum.size()) throw RangeCoderError("c and cum differ in length", RC_E_BAD_MODEL);
+    create();
+  }
+  ~Wide16Model() {
+    if (m_) rc_model_destroy(m_);
+  }
+  Wide16Model(const Wide16Model&) = delete;
+  Wide16Model& operator=(const Wide16Model&) = delete;
+  rc_model* get() const { return m_; }
+  Context& ctx() const { return *ctx_; }
+  uint64_t slot_capacity(uint64_t n) const { return detail::slot_capacity(c_, total_, n); }
+
+  // rc_encode_batch_wide16 / rc_decode_batch_wide16 on typed device pointers (asynchronous)
+  void encode_batch(const uint16_t* syms_dev, const uint64_t* sym_off_dev, uint32_t n_chunks,
+                    uint8_t* out_dev, const uint64_t* out_off_dev, uint64_t* out_len_dev,
+                    uint32_t* flags_dev) const {
+    check(rc_encode_batch_wide16(ctx_->get(), m_, syms_dev, sym_off_dev, n_chunks, out_dev,
+                                 out_off_dev, out_len_dev, flags_dev),
+          "rc_encode_batch_wide16");
+  }
+  void decode_batch(const uint8_t* code_dev, const uint64_t* code_off_dev,
+                    const uint64_t* code_len_dev, uint16_t* syms_out_dev,
+                    const uint64_t* sym_off_dev, uint32_t n_chunks, uint32_t* flags_dev) const {
+    check(rc_decode_batch_wide16(ctx_->get(), m_, code_dev, code_off_dev, code_len_dev,
+                                 syms_out_dev, sym_off_dev, n_chunks, flags_dev),
+          "rc_decode_batch_wide16");
+  }
+
+  // Encode many independent chunks of 16-bit symbols in one launch.
+  std::vector<std::vector<uint8_t>> encode_chunks(
+      const std::vector<std::vector<uint16_t>>& chunks) const {
+    std::vector<uint64_t> sym_off;
+    const auto syms = detail::concat<uint16_t>(
+        (uint32_t)chunks.size(),
+        [&](uint32_t k) -> const std::vector<uint16_t>& { return chunks[k]; }, sym_off);
+    return detail::encode_chunks(
+        ctx_->get(), syms, sym_off, [&](uint64_t len) { return slot_capacity(len); },
+        [&](const uint16_t* s, const uint64_t* soff, uint32_t nc, uint8_t* out,
+            const uint64_t* ooff, uint64_t* len, uint32_t* flags) {
+          encode_batch(s, soff, nc, out, ooff, len, flags);
+        });
+  }
+
+  // Decode many independent streams; counts[k] symbols each (out-of-band,
+  // sample_impl.rs:113-120)
+  std::vector<std::vector<uint16_t>> decode_chunks(const std::vector<std::vector<uint8_t>>& codes,
+                                                   const std::vector<uint64_t>& counts) const {
+    return detail::decode_chunks<uint16_t>(
+        ctx_->get(), (uint32_t)codes.size(),
+        [&](uint32_t k) -> const std::vector<uint8_t>& { return codes[k]; },
+        [&](uint32_t k) { return counts.at(k); },
+        [&](const uint8_t* code, const uint64_t* coff, const uint64_t* clen, uint16_t* syms,
+            const uint64_t* soff, uint32_t nc, uint32_t* flags) {
+          decode_batch(code, coff, clen, syms, soff, nc, flags);
+        });
+  }
+
+ private:
+  void create() {
+    check(rc_model_create_static_wide16(ctx_->get(), (uint32_t)c_.size(), c_.data(), cum_.data(),
+                                        total_, &m_),
+          "rc_model_create_static_wide16");
+  }
+  Context* ctx_;
+  rc_model* m_ = nullptr;
+  std::vector<uint32_t> c_, cum_;
+  uint32_t total_ = 0;
+};
 #endif  // the HIP runtime API header
 
 // RangeCoder (src/range_coder.rs:7-146): the public accessors of a coder state (a snapshot: a

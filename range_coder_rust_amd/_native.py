@@ -48,12 +48,15 @@ EXPORTS = (
     "rc_checksum_batch", "rc_container2_info_parse", "rc_container2_pack",
     "rc_container2_offsets", "rc_container2_model", "rc_container2_verify",
     "rc_cluster_contexts_dev",
+    "rc_model_create_static_wide16", "rc_encode_batch_wide16", "rc_decode_batch_wide16",
+    "rc_quantize_counts_wide16",
     "rc_model_create_order1_set_lagged", "rc_histogram_pairs_lagged",
     "rc_model_create_chunk_set", "rc_encode_batch_chunk_set", "rc_decode_batch_chunk_set",
     "rc_cost_table", "rc_chunk_set_costs", "rc_histogram_by_class",
 )
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
+MAX_WIDE16_SYMBOLS = 65536  # RC_MAX_WIDE16_SYMBOLS
 RC_E_BAD_CONTAINER = -6
 RC_E_CAPACITY = -7
 RC_E_BAD_SYMBOL = -8
@@ -282,9 +285,27 @@ def load():
         L.rc_chunk_group_.restype = _I
         L.rc_chunk_last_.argtypes = [_P, _P]
         L.rc_chunk_last_.restype = _I
+    # wide16 static models (a library of an earlier revision has none of these)
+    w16 = ("rc_model_create_static_wide16", "rc_encode_batch_wide16", "rc_decode_batch_wide16",
+           "rc_quantize_counts_wide16")
+    old7 = not hasattr(L, w16[0])
+    if not old7:
+        L.rc_model_create_static_wide16.argtypes = [_P, _U32, _P, _P, _U32, ctypes.POINTER(_P)]
+        L.rc_encode_batch_wide16.argtypes = [_P, _P, _P, _P, _U32, _P, _P, _P, _P]
+        L.rc_decode_batch_wide16.argtypes = [_P, _P, _P, _P, _P, _P, _P, _U32, _P]
+        L.rc_quantize_counts_wide16.argtypes = [_P, _U32, _U64, _U32, _P, _P, _P]
+        # host-only hooks (not in the header; tests/test_wide16_model.py, test_gpu_wide16.py):
+        # the constructor's validation, the plan (8 words) and the lanes per workgroup of the
+        # process's last wide16 encode and decode launch
+        L.rc_model_wide16_check_.argtypes = [_U32, _P, _P, _U32]
+        L.rc_model_wide16_check_.restype = _I
+        L.rc_model_wide16_plan_.argtypes = [_U32, _U32, _P]
+        L.rc_model_wide16_plan_.restype = _I
+        L.rc_wide16_last_lanes_.argtypes = [_P]
+        L.rc_wide16_last_lanes_.restype = None
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit) \
-                and not (old6 and name in cset) \
+                and not (old6 and name in cset) and not (old7 and name in w16) \
                 and not (old2 and name in c2) and not (old3 and name in per) \
                 and not (old4 and name in cj) and not (old5 and name in lag):
             getattr(L, name).restype = _I

@@ -631,6 +631,11 @@ class WideStaticModel:
 
     The table is validated on the host at construction (ValueError); the device snapshot is made
     on first use, so a model can be built and inspected without a device."""
+    # (the native calls and the cap, which Wide16StaticModel replaces)
+    _CHECK = "rc_model_wide_check_"
+    _CREATE = "rc_model_create_static_wide"
+    _MAX = N.MAX_WIDE_SYMBOLS
+    _WHAT = "wide"
 
     def __init__(self, c_freq, cum_freq=None, total_freq=None, ctx=None):
         c = np.ascontiguousarray(c_freq, dtype=np.uint32)
@@ -650,12 +655,12 @@ class WideStaticModel:
         self.n_symbols = len(c)
         self._ctx = ctx
         self._handle = None
-        rc = N.load().rc_model_wide_check_(self.n_symbols, ctypes.c_void_p(c.ctypes.data),
-                                           ctypes.c_void_p(cum.ctypes.data),
-                                           ctypes.c_uint32(self.total & 0xFFFFFFFF))
+        rc = getattr(N.load(), self._CHECK)(self.n_symbols, ctypes.c_void_p(c.ctypes.data),
+                                            ctypes.c_void_p(cum.ctypes.data),
+                                            ctypes.c_uint32(self.total & 0xFFFFFFFF))
         if rc != N.RC_OK or self.total > 0xFFFFFFFF:
             raise ValueError(
-                f"wide model rejected: need 1..{N.MAX_WIDE_SYMBOLS} symbols, total_freq in "
+                f"{self._WHAT} model rejected: need 1..{self._MAX} symbols, total_freq in "
                 "256..65536, cum[0] == 0, cum[i+1] == cum[i] + c[i], sum(c) == total_freq")
 
     @classmethod
@@ -684,10 +689,10 @@ class WideStaticModel:
     def handle(self):
         if self._handle is None:
             h = ctypes.c_void_p()
-            N.check(self.ctx._lib.rc_model_create_static_wide(
+            N.check(getattr(self.ctx._lib, self._CREATE)(
                 self.ctx.handle, self.n_symbols, ctypes.c_void_p(self.c.ctypes.data),
                 ctypes.c_void_p(self.cum.ctypes.data), ctypes.c_uint32(self.total),
-                ctypes.byref(h)), "rc_model_create_static_wide")
+                ctypes.byref(h)), self._CREATE)
             self._handle = h
         return self._handle
 
@@ -697,6 +702,42 @@ class WideStaticModel:
 
     close = StaticModelSet.close
     __del__ = StaticModel.__del__
+
+
+class Wide16StaticModel(WideStaticModel):
+    """rc_model_create_static_wide16: one static table over an alphabet of up to 65536 16-bit
+    symbols, its tables in device memory, for the wide16 batch calls, which code uint16 symbols
+    exactly as encode(&table, sym[i]) / decode(&table).  For a table a WideStaticModel accepts
+    too, both give the same bytes; the two kinds do not mix: every call but the wide16 ones
+    refuses this model (RC_E_ARG from the library), and the wide16 calls refuse every other.
+
+    The table is validated on the host at construction (ValueError); the device tables are made
+    on first use, so a model can be built and inspected without a device."""
+    _CHECK = "rc_model_wide16_check_"
+    _CREATE = "rc_model_create_static_wide16"
+    _MAX = N.MAX_WIDE16_SYMBOLS
+    _WHAT = "wide16"
+
+    @classmethod
+    def from_counts(cls, counts, target_total=65536, ctx=None):
+        """A histogram scaled to target_total with every symbol kept encodable
+        (rc_quantize_counts_wide16 with RC_Q_ALL_SYMBOLS; more symbols than target_total is a
+        ValueError)."""
+        from .model_build import quantize_counts_wide16
+        c, cum, total = quantize_counts_wide16(counts, target_total, all_symbols=True)
+        return cls(c, cum, total, ctx=ctx)
+
+    def plan(self):
+        """rc_model_wide16_plan_: what the launchers use for this table, as a dict."""
+        out = (ctypes.c_uint32 * 8)()
+        N.check(N.load().rc_model_wide16_plan_(self.n_symbols, self.total, out),
+                "rc_model_wide16_plan_")
+        keys = ("enc_lanes", "enc_lds", "enc_layout", "enc_table_bytes", "dec_lanes", "dec_lds",
+                "dec_symof_bits", "dec_shift")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d["dec_symof_bytes"] = 2 << d["dec_symof_bits"]
+        d["dec_row_bytes"] = 4 * (self.n_symbols + 2)
+        return d
 
 
 # ----------------------------------------------------------------------------- batch API
@@ -1061,6 +1102,33 @@ def decode_batch_wide(model, code, code_off, code_len, syms_out, sym_off, flags=
     syms_out uint16[...] (or int16, written as uint16).  Returns flags."""
     return _decode_batch("rc_decode_batch_wide", model, code, code_off, code_len, None, syms_out,
                          sym_off, flags, wide=True)
+
+
+def encode_batch_wide16(model, syms, sym_off, out, out_off, out_len=None, flags=None):
+    """rc_encode_batch_wide16 on torch tensors (async on torch's current stream):
+    encode_batch_wide against a Wide16StaticModel (up to 65536 symbols).
+    Returns (out_len, flags)."""
+    return _encode_batch("rc_encode_batch_wide16", model, syms, None, sym_off, out, out_off,
+                         out_len, flags, wide=True)
+
+
+def decode_batch_wide16(model, code, code_off, code_len, syms_out, sym_off, flags=None):
+    """rc_decode_batch_wide16 on torch tensors (async on torch's current stream):
+    decode_batch_wide against a Wide16StaticModel.  Returns flags."""
+    return _decode_batch("rc_decode_batch_wide16", model, code, code_off, code_len, None,
+                         syms_out, sym_off, flags, wide=True)
+
+
+def encode_chunks_wide16(model, chunks, raise_on_error=True):
+    """encode_chunks_wide against a Wide16StaticModel.  Returns a list of bytes."""
+    return _encode_chunks(encode_batch_wide16, model, [_u16_chunk(c) for c in chunks], None,
+                          raise_on_error)
+
+
+def decode_chunks_wide16(model, codes, counts, raise_on_error=True):
+    """decode_chunks_wide against a Wide16StaticModel.  Returns a list of uint16 arrays."""
+    return _decode_chunks(decode_batch_wide16, model, codes, counts, None, raise_on_error,
+                          wide=True)
 
 
 def encode_chunks_wide(model, chunks, raise_on_error=True):

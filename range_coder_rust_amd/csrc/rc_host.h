@@ -9,6 +9,7 @@
 #include "rc_indexed.h"
 #include "rc_order1.h"
 #include "rc_wide.h"
+#include "rc_wide16.h"
 #include "rc_chunk_set.h"
 
 struct rc_ctx {
@@ -30,7 +31,8 @@ enum {
   RC_KIND_SET = 2,
   RC_KIND_WIDE = 3,
   RC_KIND_ORDER1 = 4,
-  RC_KIND_CHUNK_SET = 5
+  RC_KIND_CHUNK_SET = 5,
+  RC_KIND_WIDE16 = 6
 };
 
 struct rc_model {
@@ -41,6 +43,8 @@ struct rc_model {
   SetPlan plan;
   WideArgs wide;
   WidePlan wplan;
+  Wide16Args w16;  // kind 6, a wide16 static model (rc_wide16.h): `w16` and `w16plan`
+  Wide16Plan w16plan;
   ChunkSetArgs cset;  // kind 5, a static chunk set (rc_chunk_set.h): `args` is row 0's
   O1Args o1;  // kind 4 (o1.period: 1, 2, 4 or 8)
   u32 o1_lag;  // kind 4: 1, 2, 4 or 8 (rc_order1.h: no field of the kernels' O1Args)

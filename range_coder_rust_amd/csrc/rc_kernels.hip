@@ -56,6 +56,8 @@ __global__ __launch_bounds__(WG) void k_synth_generic(u64 seed, const uint8_t* _
 #include <cmath>
 #include <vector>
 
+#include "rc_wide16_tables.h"
+
 // The only place the library reads its environment (tests/test_abi.py checks that no other
 // source calls getenv): once per context, in rc_ctx_create.
 RcKnobs rc_knobs_from_env() {
@@ -1243,6 +1245,95 @@ rc_status rc_decode_batch_wide(rc_ctx* ctx, const rc_model* wide, const uint8_t*
                       return rc_wide_decode_launch(ctx->cur, ctx->knobs, wide->wide, wide->div,
                                                    wide->wplan, code, code_off, code_len,
                                                    (uint16_t*)syms_out, sym_off, n_chunks, flags);
+                    });
+}
+
+}  // extern "C"
+
+// ---- wide16 static models (rc_wide16.h; kernels in rc_wide16.hip) ----
+
+// what rc_model_create_static_wide16 accepts (include/range_coder.h)
+static rc_status wide16_check(u32 n_symbols, const u32* c, const u32* cum, u32 total) {
+  if (!c || !cum) return RC_E_ARG;
+  if (n_symbols < 1 || n_symbols > RC_MAX_WIDE16_SYMBOLS || total < 256 || total > 65536)
+    return RC_E_BAD_MODEL;
+  return table_ok(n_symbols, c, cum, total) ? RC_OK : RC_E_BAD_MODEL;
+}
+
+extern "C" {
+
+// Internal test hooks (not in include/range_coder.h; host only, no device needed).
+// rc_model_wide16_check_: rc_model_create_static_wide16's validation of its table.
+rc_status rc_model_wide16_check_(uint32_t n_symbols, const uint32_t* c_freq,
+                                 const uint32_t* cum_freq, uint32_t total_freq) {
+  return wide16_check(n_symbols, c_freq, cum_freq, total_freq);
+}
+// rc_model_wide16_plan_: what the launchers use for a table of n_symbols symbols and total
+// total_freq, out[8] = encoder {lanes per workgroup, dynamic LDS bytes (rings only), 0, bytes of
+// the entries in device memory}, decoder {lanes, LDS bytes, log2 of the q-to-symbol table's
+// entries, 0}.
+rc_status rc_model_wide16_plan_(uint32_t n_symbols, uint32_t total_freq, uint32_t* out) {
+  return plan_hook<Wide16Plan>(n_symbols >= 1 && n_symbols <= RC_MAX_WIDE16_SYMBOLS, total_freq,
+                               out,
+                               [&](Wide16Plan* p) { rc_wide16_plan(n_symbols, total_freq, p); });
+}
+
+rc_status rc_model_create_static_wide16(rc_ctx* ctx, uint32_t n_symbols, const uint32_t* c_freq,
+                                        const uint32_t* cum_freq, uint32_t total_freq,
+                                        rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
+  *out = nullptr;
+  const rc_status ok = wide16_check(n_symbols, c_freq, cum_freq, total_freq);
+  if (ok != RC_OK) return ok;
+  Wide16Plan plan;
+  rc_wide16_plan(n_symbols, total_freq, &plan);
+  const Wide16Tables t = wide16_build_tables(n_symbols, c_freq, cum_freq, total_freq);
+  // (the 8-B entries first: the allocation's alignment is theirs; then the row, then the halfwords)
+  const size_t enc_bytes = t.enc.size() * sizeof(u32), row_bytes = t.row.size() * sizeof(u32),
+               symof_bytes = t.symof.size() * sizeof(uint16_t);
+  rc_model* mm = nullptr;
+  char* d = nullptr;
+  const rc_status up = model_upload(
+      ctx, RC_KIND_WIDE16, total_freq,
+      {{t.enc.data(), enc_bytes}, {t.row.data(), row_bytes}, {t.symof.data(), symof_bytes}}, &mm,
+      &d);
+  if (up != RC_OK) return up;
+  mm->w16plan = plan;
+  Wide16Args& a = mm->w16;
+  small_model_args(a.m, n_symbols, total_freq, plan.dec_bits, plan.dec_shift);
+  a.enc = (const uint2*)d;
+  a.row = (const u32*)(d + enc_bytes);
+  a.symof = (const uint16_t*)(d + enc_bytes + row_bytes);
+  a.enc_clamp = t.enc_clamp;
+  a.qmask = (u32)t.symof.size() - 1u;
+  *out = mm;
+  return RC_OK;
+}
+
+rc_status rc_encode_batch_wide16(rc_ctx* ctx, const rc_model* wide16, const void* syms,
+                                 const uint64_t* sym_off, uint32_t n_chunks, uint8_t* out,
+                                 const uint64_t* out_off, uint64_t* out_len, uint32_t* flags) {
+  return batch_call(ctx, wide16, 1u << RC_KIND_WIDE16, ((uintptr_t)syms & 1u) == 0, n_chunks,
+                    syms && sym_off && out && out_off && out_len && flags,
+                    "wide16 encode launch", [&] {
+                      return rc_wide16_encode_launch(ctx->cur, ctx->knobs, wide16->w16,
+                                                     wide16->div, wide16->w16plan,
+                                                     (const uint16_t*)syms, sym_off, n_chunks,
+                                                     out, out_off, out_len, flags);
+                    });
+}
+
+rc_status rc_decode_batch_wide16(rc_ctx* ctx, const rc_model* wide16, const uint8_t* code,
+                                 const uint64_t* code_off, const uint64_t* code_len,
+                                 void* syms_out, const uint64_t* sym_off, uint32_t n_chunks,
+                                 uint32_t* flags) {
+  return batch_call(ctx, wide16, 1u << RC_KIND_WIDE16, ((uintptr_t)syms_out & 1u) == 0,
+                    n_chunks, code && code_off && code_len && syms_out && sym_off && flags,
+                    "wide16 decode launch", [&] {
+                      return rc_wide16_decode_launch(ctx->cur, ctx->knobs, wide16->w16,
+                                                     wide16->div, wide16->w16plan, code, code_off,
+                                                     code_len, (uint16_t*)syms_out, sym_off,
+                                                     n_chunks, flags);
                     });
 }
 

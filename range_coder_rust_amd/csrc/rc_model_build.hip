@@ -1125,7 +1125,8 @@ rc_status rc_ideal_bits_wide(rc_ctx* ctx, const rc_model* wide, const void* syms
 
 }  // extern "C"
 
-// rc_quantize_counts / rc_quantize_counts_wide: one rule, alphabets of up to max_symbols
+// rc_quantize_counts / rc_quantize_counts_wide / rc_quantize_counts_wide16: one rule, alphabets
+// of up to max_symbols
 static rc_status quantize_counts(const uint64_t* counts, uint32_t n_symbols, u32 max_symbols,
                                  uint64_t target_total, uint32_t qflags, uint32_t* c_out,
                                  uint32_t* cum_out, uint32_t* total_out) {
@@ -1204,6 +1205,15 @@ rc_status rc_quantize_counts_wide(const uint64_t* counts, uint32_t n_symbols,
                                   uint64_t target_total, uint32_t qflags, uint32_t* c_out,
                                   uint32_t* cum_out, uint32_t* total_out) {
   return quantize_counts(counts, n_symbols, RC_MAX_WIDE_SYMBOLS, target_total, qflags, c_out,
+                         cum_out, total_out);
+}
+
+rc_status rc_quantize_counts_wide16(const uint64_t* counts, uint32_t n_symbols,
+                                    uint64_t target_total, uint32_t qflags, uint32_t* c_out,
+                                    uint32_t* cum_out, uint32_t* total_out) {
+  // every symbol kept encodable needs a frequency of its own: no target below n can hold them
+  if ((qflags & RC_Q_ALL_SYMBOLS) && target_total && n_symbols > target_total) return RC_E_ARG;
+  return quantize_counts(counts, n_symbols, RC_MAX_WIDE16_SYMBOLS, target_total, qflags, c_out,
                          cum_out, total_out);
 }
 

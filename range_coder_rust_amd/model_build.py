@@ -26,6 +26,8 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
                                   order-1 set, straight from the symbols (HIP)
   histogram_wide(syms, sym_off, n_bins)      rc_histogram_wide: the counts of 16-bit symbols (HIP)
   build_wide_model(syms, sym_off, n)         those counts -> WideStaticModel, in one call
+  histogram16(syms, sym_off)                 the exact 65536-bin histogram of 16-bit symbols (HIP)
+  build_wide16_model(syms, sym_off)          those counts -> Wide16StaticModel, in one call
   ideal_bits_wide(model, syms, sym_off)      rc_ideal_bits_wide: per-chunk ideal bits of a wide
                                   model, straight from the symbols (HIP)
   cost_table(c, total)            rc_cost_table: a row's integer costs, 2^-16 bit units (host)
@@ -40,7 +42,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from .api import (ChunkModelSet, Order1ModelSet, StaticModel, WideStaticModel, _check_dev, _ptr, _sym16, _torch,
+from .api import (ChunkModelSet, Order1ModelSet, StaticModel, Wide16StaticModel, WideStaticModel, _check_dev, _ptr, _sym16, _torch,
                   default_context)
 
 
@@ -69,6 +71,15 @@ def quantize_counts_wide(counts, target_total=0, all_symbols=False):
     """rc_quantize_counts_wide (host): quantize_counts for the alphabets of wide static models
     (len n <= 4096)."""
     return quantize_counts(counts, target_total, all_symbols, _entry="rc_quantize_counts_wide")
+
+
+def quantize_counts_wide16(counts, target_total=0, all_symbols=False):
+    """rc_quantize_counts_wide16 (host): quantize_counts for the alphabets of wide16 static models
+    (len n <= 65536).  all_symbols with more symbols than a nonzero target_total is a
+    ValueError."""
+    if all_symbols and target_total and len(counts) > target_total:
+        raise ValueError("all_symbols needs target_total >= the number of symbols")
+    return quantize_counts(counts, target_total, all_symbols, _entry="rc_quantize_counts_wide16")
 
 
 def histogram(syms, sym_off, per_chunk=False, batch=True, ctx=None):
@@ -443,6 +454,47 @@ def build_wide_model(syms, sym_off, n_symbols, target_total=1 << 16, all_symbols
     counts = hist.cpu().numpy().astype(np.uint64)
     c, cum, total = quantize_counts_wide(counts, target_total, all_symbols)
     return WideStaticModel(c, cum, total, ctx=ctx)
+
+
+def histogram16(syms, sym_off, ctx=None):
+    """The exact histogram of 16-bit symbols over all 65536 values: int64[65536] tensor (async,
+    torch's current stream).  syms uint16 / int16 on the device, sym_off in symbols.
+
+    No kernel of its own: the pair histogram of period 2 over the symbols' bytes (byte offsets
+    2 * sym_off) counts at phase 1 the pairs (low byte, high byte) of one symbol each, and phase 1
+    never crosses a chunk start, so on a little-endian host slice [1][lo][hi] is the count of
+    symbol hi << 8 | lo."""
+    import sys
+    torch = _torch()
+    _sym16(syms, "syms")
+    _check_dev(sym_off, "sym_off", (torch.int64, torch.uint64))
+    if sys.byteorder != "little":
+        raise NotImplementedError("histogram16 reads the symbols' bytes in little-endian order")
+    pair, _ = histogram_pairs_periodic(syms.view(torch.uint8), sym_off * 2, 2, ctx=ctx)
+    return pair[1].t().contiguous().view(-1)
+
+
+def build_wide16_model(syms, sym_off, n_symbols=None, target_total=1 << 16, ctx=None):
+    """histogram16 of the batch, then a Wide16StaticModel of its table scaled to target_total over
+    n_symbols symbols (None: the largest symbol that occurs, plus one).  Every symbol that occurs
+    gets c >= 1; one that does not may get 0 and is then not encodable.  Raises ValueError when a
+    symbol >= n_symbols occurs, when nothing occurs, or when more distinct symbols occur than
+    target_total.  Synchronises (the counts are quantized on the host)."""
+    counts = histogram16(syms, sym_off, ctx=ctx).cpu().numpy().astype(np.uint64)
+    used = np.flatnonzero(counts)
+    if used.size == 0:
+        raise ValueError("no symbols to model")
+    if n_symbols is None:
+        n_symbols = int(used[-1]) + 1
+    n_symbols = int(n_symbols)
+    if not 1 <= n_symbols <= N.MAX_WIDE16_SYMBOLS:
+        raise ValueError(f"n_symbols must be 1..{N.MAX_WIDE16_SYMBOLS}")
+    if used[-1] >= n_symbols:
+        raise ValueError(f"symbol {int(used[-1])} >= n_symbols in the data")
+    if target_total and used.size > target_total:
+        raise ValueError(f"{used.size} distinct symbols occur: more than target_total")
+    c, cum, total = quantize_counts_wide16(counts[:n_symbols], target_total, all_symbols=False)
+    return Wide16StaticModel(c, cum, total, ctx=ctx)
 
 
 def ideal_bits_wide(model, syms, sym_off):

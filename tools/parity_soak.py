@@ -29,11 +29,15 @@ A third of the iterations instead draw one of:
               in [256, 2^16], 1 .. 1500 ragged chunks with a random class each (now and then one
               that names no row: RC_F_BAD_MODEL), against the oracle chunk by chunk with the
               chunk's row, and the round trip
+  wide16      a wide16 static model (rc_model_create_static_wide16) over n symbols, n log-uniform
+              in 257 .. 65536, total in [256, 2^16], dense or with runs of zero frequencies,
+              1 .. 1500 ragged chunks of 16-bit symbols, against orc_stream_encode fed each
+              symbol's triple chunk by chunk, and the round trip
 Prints a progress line per iteration and one JSON summary line; exits 1 at the first mismatch
 (after printing what differed).  The oracle is the checker here, never the thing measured.
 
 Usage (GPU box): python3 tools/parity_soak.py [seconds] [seed] [draw]
-(draw: only this one of adaptive, stream-enc, stream-dec, chunk-set)
+(draw: only this one of adaptive, stream-enc, stream-dec, chunk-set, wide16)
 """
 import json
 import math
@@ -325,12 +329,65 @@ def chunk_set_iteration(rng):
     return (f"chunk-set K={K} total={total} chunks={n}", n, int(lens.sum()), int(g_len.sum()), bad)
 
 
+def wide16_iteration(rng):
+    n_sym = int(round(math.exp(rng.uniform(math.log(257), math.log(65536)))))
+    total = int(rng.choice([256, 4096, 65535, 65536, int(rng.integers(256, 65537))]))
+    p = rng.random(n_sym) ** 6 + 1e-6
+    live = min(n_sym, total, int(rng.choice([n_sym, max(1, n_sym // 7),
+                                             int(rng.integers(1, n_sym + 1))])))
+    if live < n_sym:  # zero frequencies (never drawn in the data), in runs as well as scattered
+        keep = rng.permutation(n_sym)[:live] if rng.random() < 0.5 else \
+            (int(rng.integers(0, n_sym)) + np.arange(live)) % n_sym
+        q = np.zeros(n_sym)
+        q[keep] = p[keep]
+        p = q
+    c = quantise(p, total, rng).astype(np.uint32)
+    cum = np.concatenate([[0], np.cumsum(c.astype(np.uint64))[:-1]]).astype(np.uint32)
+    m = rc.Wide16StaticModel(c, cum, total)
+    n = int(rng.choice([1, 2, 255, 256, 257, 1024, int(rng.integers(1, 1501))]))
+    lens = rng.choice([0, 1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 300, 1000], n).astype(np.int64)
+    occupied = np.flatnonzero(c)
+    w = c[occupied].astype(np.float64)
+    data = occupied[rng.choice(len(occupied), int(lens.sum()) + 1,
+                               p=w / w.sum())].astype(np.uint16)
+    sym_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    caps = np.array([rc.slot_capacity(int(L), m.max_bits_per_symbol() + 0.5, slack=1.05)
+                     for L in lens], np.int64)
+    out_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64) + int(rng.integers(0, 16))
+    d_syms = torch.from_numpy(data.view(np.int16)).cuda()
+    d_soff = torch.from_numpy(sym_off).cuda()
+    d_out = torch.zeros(int(out_off[-1]) + 16, dtype=torch.uint8, device="cuda")
+    ol, fe = rc.encode_batch_wide16(m, d_syms, d_soff, d_out, torch.from_numpy(out_off).cuda())
+    dec = torch.zeros(int(sym_off[-1]) + 16, dtype=torch.int16, device="cuda")
+    fd = rc.decode_batch_wide16(m, d_out, torch.from_numpy(out_off[:-1].copy()).cuda(), ol, dec,
+                                d_soff)
+    torch.cuda.synchronize()
+    g_out, g_len, g_fe, g_fd = (t.cpu().numpy() for t in (d_out, ol, fe, fd))
+    g_dec = dec.cpu().numpy().view(np.uint16)
+    bad = []
+    for k in range(n):
+        sk = data[sym_off[k]:sym_off[k + 1]]
+        tri = np.stack([c[sk], cum[sk], np.full(len(sk), total, np.uint32)], axis=1)
+        f, want, _ = cpu.stream_encode(cpu.Stream.fresh(), tri.astype(np.uint32), finish=True)
+        a, L = int(out_off[k]), len(want)
+        if f != int(g_fe[k]) or L != int(g_len[k]) or bytes(g_out[a:a + L]) != want:
+            bad.append(f"wide16 encode of chunk {k}")
+            break
+        if g_fd[k] != 0 or not np.array_equal(g_dec[sym_off[k]:sym_off[k + 1]], sk):
+            bad.append(f"wide16 decode of chunk {k}")
+            break
+    m.close()
+    return (f"wide16 n={n_sym} live={live} total={total} chunks={n}", n, int(lens.sum()),
+            int(g_len.sum()), bad)
+
+
 def main():
     budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 20260518
     only = {"adaptive": adaptive_iteration, "stream-enc": stream_enc_iteration,
             "stream-dec": stream_dec_iteration,
-            "chunk-set": chunk_set_iteration}[sys.argv[3]] if len(sys.argv) > 3 else None
+            "chunk-set": chunk_set_iteration,
+            "wide16": wide16_iteration}[sys.argv[3]] if len(sys.argv) > 3 else None
     rng = np.random.default_rng(seed)
     rc.default_context(0)
     t_end = time.time() + budget
@@ -341,7 +398,8 @@ def main():
         if other < 0.35 or only:
             fn = only or (adaptive_iteration if other < 0.1 else
                           stream_enc_iteration if other < 0.175 else
-                          stream_dec_iteration if other < 0.25 else chunk_set_iteration)
+                          stream_dec_iteration if other < 0.25 else
+                          chunk_set_iteration if other < 0.31 else wide16_iteration)
             name, n, nsym, nbytes, bad = fn(rng)
             it += 1
             chunks += n
