@@ -456,7 +456,8 @@ rc_status rc_decode_batch_wide(rc_ctx* ctx, const rc_model* wide, const uint8_t*
  * two or not) and the table passes rc_model_create_static's checks; anything else is
  * RC_E_BAD_MODEL.  Zero-frequency symbols are allowed (an alphabet of 2^16 symbols with a total
  * below 2^16 needs them).  The total stays in the small-model regime for the wide models'
- * reason; totals above 2^16 are not supported.  The tables (at most 512 KiB of encoder entries,
+ * reason; a table whose total lies above 2^16 belongs to a wide16 fine model
+ * (rc_model_create_static_wide16_fine, below), which the same batch calls code.  The tables (at most 512 KiB of encoder entries,
  * 128 KiB of q-to-symbol halfwords and a cum row) are built by the constructor in device memory
  * and read through the L2; the decoder's workgroups stage the halfwords in a CU's local memory
  * beside their rings.
@@ -482,6 +483,50 @@ rc_status rc_decode_batch_wide16(rc_ctx* ctx, const rc_model* wide16, const uint
                                  const uint64_t* code_off_dev, const uint64_t* code_len_dev,
                                  void* syms16_out_dev, const uint64_t* sym_off_dev,
                                  uint32_t n_chunks, uint32_t* flags_dev);
+
+/* ---- wide16 fine models: totals up to 2^24 for the full 16-bit alphabet ----
+ * A wide16 fine model is a wide16 static model whose total lies above 2^16: one frequency in 2^16
+ * is too coarse once thousands of symbols are rare, and a table over all 2^16 symbols with every
+ * symbol encodable is all ones at a total of 2^16.
+ *
+ * Accepted when 1 <= n_symbols <= RC_MAX_WIDE16_SYMBOLS, 65536 < total_freq <=
+ * RC_MAX_WIDE16_FINE_TOTAL (a power of two or not) and the table passes rc_model_create_static's
+ * checks; anything else is RC_E_BAD_MODEL, a total of at most 65536 included: such a table is
+ * rc_model_create_static_wide16's, so every table has exactly one constructor.  Zero-frequency
+ * symbols are allowed.
+ *
+ * Coding goes through rc_encode_batch_wide16 / rc_decode_batch_wide16, which take a wide16 model
+ * of either constructor, and the contract is theirs word for word: symbol i of chunk k is coded
+ * exactly as encoder.encode(&table, sym[i]) and decoded exactly as decoder.decode(&table) with
+ * FreqTable::find_index over the table (among equal cum values the last is chosen, and the result
+ * is n_symbols-1 when rfreq >= total); bytes, lengths and flags are bit-identical to the
+ * reference arithmetic.  RC_F_BAD_SYMBOL, RC_F_ZERO_FREQ, the RC_F_CAPACITY length rule,
+ * RC_F_TOO_LONG, RC_F_TRUNCATED, RC_F_CORRUPT, first-error-wins and the over-read and touch rules
+ * are unchanged.  Every other entry point that takes a model returns RC_E_ARG for a fine model,
+ * as for a wide16 model.
+ *
+ * Bytes per symbol.  A symbol starts with range >= 2^48, so range / total >= 2^24 and the
+ * symbol's range r * c is at least 2^24; no_carry_expansion settles k bytes only while that range
+ * is below 2^(64 - 8k), so at most 4 (3 at totals up to 2^16), and range_reduction_expansion at
+ * most 7 more: one symbol settles at most 11 bytes, and 8 + 11 n bytes hold every chunk of n
+ * symbols (RC_STREAM_MAX_BYTES' 12 n + 8 covers it).  That bound is met only where
+ * range_reduction_expansion cuts the range down to the part below a byte boundary it straddles,
+ * which costs log2(range / part) bits: 1.44 bits on average, on fewer than one symbol in 256.
+ * The size to plan an output slot with is therefore the ideal one, log2(total / c) bits per
+ * symbol (up to 24), plus the flush's 8 bytes and a little slack; a slot that turns out too
+ * small is RC_F_CAPACITY with the exact length, as ever.  A slot sized that
+ * way carries no guarantee: only 8 + 11 n bytes are certain to hold a chunk of n symbols, and a
+ * caller who sizes by the ideal cost must check the flags and encode a flagged chunk again.
+ *
+ * The tables (at most 512 KiB of encoder entries; for the decoder the occupied symbols, their
+ * cum row and a bucket table over the top bits of the scaled code value, at most 512 KiB together)
+ * are built by the constructor in device memory; the decoder's workgroups stage the bucket table
+ * in a CU's local memory beside their rings.  Destroy the model with rc_model_destroy.          */
+#define RC_MAX_WIDE16_FINE_TOTAL (1u << 24)
+rc_status rc_model_create_static_wide16_fine(rc_ctx* ctx, uint32_t n_symbols,
+                                             const uint32_t* c_freq_host,
+                                             const uint32_t* cum_freq_host, uint32_t total_freq,
+                                             rc_model** out);
 
 /* ---- synchronous host-memory helpers (stage through device memory, wait for completion;
  *      returns RC_E_CHUNK when any chunk is flagged — flags are still filled in).  Their
@@ -810,6 +855,12 @@ rc_status rc_quantize_counts_wide16(const uint64_t* counts_host, uint32_t n_symb
                                     uint64_t target_total, uint32_t qflags,
                                     uint32_t* c_out_host, uint32_t* cum_out_host,
                                     uint32_t* total_out_host);
+/* The same rule for the totals of wide16 fine models: 65536 < target_total <=
+ * RC_MAX_WIDE16_FINE_TOTAL, anything else (0, the exact table, included) is RC_E_ARG.        */
+rc_status rc_quantize_counts_wide16_fine(const uint64_t* counts_host, uint32_t n_symbols,
+                                         uint64_t target_total, uint32_t qflags,
+                                         uint32_t* c_out_host, uint32_t* cum_out_host,
+                                         uint32_t* total_out_host);
 
 /* Batched PModel::ideal_code_length (pmodel.rs:14-40): bits_dev[k] = sum over symbols s of
  * chunk k of log2(total / c[s]) = sum_i hist[k][i] * (ln total - ln c_i) / ln 2, in f64,

@@ -722,21 +722,10 @@ class WideModel {
 // alphabet WideModel accepts too, both give the same bytes.
 class Wide16Model {
  public:
-  Wide16Model(Context& ctx, const PModel& pm) : ctx_(&ctx) {
-    const uint32_t n = (uint32_t)pm.alphabet_count();
-    for (uint32_t i = 0; i < n; ++i) {
-      c_.push_back(pm.c_freq(i));
-      cum_.push_back(pm.cum_freq(i));
-    }
-    total_ = pm.total_freq();
-    create();
-  }
+  Wide16Model(Context& ctx, const PModel& pm) : Wide16Model(ctx, pm, false) {}
   Wide16Model(Context& ctx, const std::vector<uint32_t>& c, const std::vector<uint32_t>& cum,
               uint32_t total)
-      : ctx_(&ctx), c_(c), cum_(cum), total_(total) {
-    if (c.size() != cum.size()) throw RangeCoderError("c and cum differ in length", RC_E_BAD_MODEL);
-    create();
-  }
+      : Wide16Model(ctx, c, cum, total, false) {}
   ~Wide16Model() {
     if (m_) rc_model_destroy(m_);
   }
@@ -791,16 +780,50 @@ class Wide16Model {
         });
   }
 
+ protected:
+  // fine: the table is a wide16 fine model's (Wide16FineModel), which the same batch calls code
+  Wide16Model(Context& ctx, const PModel& pm, bool fine) : ctx_(&ctx) {
+    const uint32_t n = (uint32_t)pm.alphabet_count();
+    for (uint32_t i = 0; i < n; ++i) {
+      c_.push_back(pm.c_freq(i));
+      cum_.push_back(pm.cum_freq(i));
+    }
+    total_ = pm.total_freq();
+    create(fine);
+  }
+  Wide16Model(Context& ctx, const std::vector<uint32_t>& c, const std::vector<uint32_t>& cum,
+              uint32_t total, bool fine)
+      : ctx_(&ctx), c_(c), cum_(cum), total_(total) {
+    if (c.size() != cum.size()) throw RangeCoderError("c and cum differ in length", RC_E_BAD_MODEL);
+    create(fine);
+  }
+
  private:
-  void create() {
-    check(rc_model_create_static_wide16(ctx_->get(), (uint32_t)c_.size(), c_.data(), cum_.data(),
-                                        total_, &m_),
-          "rc_model_create_static_wide16");
+  void create(bool fine) {
+    if (fine)
+      check(rc_model_create_static_wide16_fine(ctx_->get(), (uint32_t)c_.size(), c_.data(),
+                                               cum_.data(), total_, &m_),
+            "rc_model_create_static_wide16_fine");
+    else
+      check(rc_model_create_static_wide16(ctx_->get(), (uint32_t)c_.size(), c_.data(),
+                                          cum_.data(), total_, &m_),
+            "rc_model_create_static_wide16");
   }
   Context* ctx_;
   rc_model* m_ = nullptr;
   std::vector<uint32_t> c_, cum_;
   uint32_t total_ = 0;
+};
+
+// A wide16 fine model (rc_model_create_static_wide16_fine): Wide16Model's interface for a table
+// whose total lies above 2^16, up to RC_MAX_WIDE16_FINE_TOTAL (2^24).  A table with a smaller total
+// is Wide16Model's and is refused here.
+class Wide16FineModel : public Wide16Model {
+ public:
+  Wide16FineModel(Context& ctx, const PModel& pm) : Wide16Model(ctx, pm, true) {}
+  Wide16FineModel(Context& ctx, const std::vector<uint32_t>& c, const std::vector<uint32_t>& cum,
+                  uint32_t total)
+      : Wide16Model(ctx, c, cum, total, true) {}
 };
 #endif  // the HIP runtime API header
 

@@ -11,7 +11,7 @@ from .api import (  # noqa: F401
     decode_chunks_indexed,
     WideStaticModel, encode_batch_wide, decode_batch_wide, encode_chunks_wide,
     decode_chunks_wide,
-    Wide16StaticModel, encode_batch_wide16, decode_batch_wide16, encode_chunks_wide16,
+    Wide16StaticModel, Wide16FineModel, encode_batch_wide16, decode_batch_wide16, encode_chunks_wide16,
     decode_chunks_wide16,
     Order1ModelSet, encode_batch_order1, decode_batch_order1, encode_chunks_order1,
     decode_chunks_order1,
@@ -25,6 +25,7 @@ from .model_build import build_model, histogram, ideal_bits, quantize_counts, qu
 from .model_build import build_order1_set, histogram_order1  # noqa: F401
 from .model_build import build_wide_model, histogram_wide, ideal_bits_wide  # noqa: F401
 from .model_build import build_wide16_model, histogram16, quantize_counts_wide16  # noqa: F401
+from .model_build import quantize_counts_wide16_fine  # noqa: F401
 from .model_build import (cluster_contexts, cluster_contexts_joint, fit_order1_set,  # noqa: F401
                           histogram_pairs, histogram_pairs_periodic, ideal_bits_order1)
 from .model_build import (chunk_set_costs, cost_table, fit_chunk_set,  # noqa: F401

@@ -50,6 +50,7 @@ EXPORTS = (
     "rc_cluster_contexts_dev",
     "rc_model_create_static_wide16", "rc_encode_batch_wide16", "rc_decode_batch_wide16",
     "rc_quantize_counts_wide16",
+    "rc_model_create_static_wide16_fine", "rc_quantize_counts_wide16_fine",
     "rc_model_create_order1_set_lagged", "rc_histogram_pairs_lagged",
     "rc_model_create_chunk_set", "rc_encode_batch_chunk_set", "rc_decode_batch_chunk_set",
     "rc_cost_table", "rc_chunk_set_costs", "rc_histogram_by_class",
@@ -57,6 +58,7 @@ EXPORTS = (
 MAX_SET_MODELS = 64  # RC_MAX_SET_MODELS
 MAX_WIDE_SYMBOLS = 4096  # RC_MAX_WIDE_SYMBOLS
 MAX_WIDE16_SYMBOLS = 65536  # RC_MAX_WIDE16_SYMBOLS
+MAX_WIDE16_FINE_TOTAL = 1 << 24  # RC_MAX_WIDE16_FINE_TOTAL
 RC_E_BAD_CONTAINER = -6
 RC_E_CAPACITY = -7
 RC_E_BAD_SYMBOL = -8
@@ -303,9 +305,25 @@ def load():
         L.rc_model_wide16_plan_.restype = _I
         L.rc_wide16_last_lanes_.argtypes = [_P]
         L.rc_wide16_last_lanes_.restype = None
+    # wide16 fine models (a library of an earlier revision has none of these)
+    w16f = ("rc_model_create_static_wide16_fine", "rc_quantize_counts_wide16_fine")
+    old8 = not hasattr(L, w16f[0])
+    if not old8:
+        L.rc_model_create_static_wide16_fine.argtypes = [_P, _U32, _P, _P, _U32,
+                                                         ctypes.POINTER(_P)]
+        L.rc_quantize_counts_wide16_fine.argtypes = [_P, _U32, _U64, _U32, _P, _P, _P]
+        # host-only hooks (not in the header; tests/test_wide16_fine_model.py,
+        # test_gpu_wide16_fine.py): as the wide16 ones
+        L.rc_model_wide16_fine_check_.argtypes = [_U32, _P, _P, _U32]
+        L.rc_model_wide16_fine_check_.restype = _I
+        L.rc_model_wide16_fine_plan_.argtypes = [_U32, _U32, _P]
+        L.rc_model_wide16_fine_plan_.restype = _I
+        L.rc_wide16_fine_last_lanes_.argtypes = [_P]
+        L.rc_wide16_fine_last_lanes_.restype = None
     for name in EXPORTS:
         if name not in ("rc_status_string", "rc_last_error") and not (old and name in fit) \
                 and not (old6 and name in cset) and not (old7 and name in w16) \
+                and not (old8 and name in w16f) \
                 and not (old2 and name in c2) and not (old3 and name in per) \
                 and not (old4 and name in cj) and not (old5 and name in lag):
             getattr(L, name).restype = _I

@@ -636,6 +636,7 @@ class WideStaticModel:
     _CREATE = "rc_model_create_static_wide"
     _MAX = N.MAX_WIDE_SYMBOLS
     _WHAT = "wide"
+    _TOTALS = "256..65536"
 
     def __init__(self, c_freq, cum_freq=None, total_freq=None, ctx=None):
         c = np.ascontiguousarray(c_freq, dtype=np.uint32)
@@ -661,7 +662,7 @@ class WideStaticModel:
         if rc != N.RC_OK or self.total > 0xFFFFFFFF:
             raise ValueError(
                 f"{self._WHAT} model rejected: need 1..{self._MAX} symbols, total_freq in "
-                "256..65536, cum[0] == 0, cum[i+1] == cum[i] + c[i], sum(c) == total_freq")
+                f"{self._TOTALS}, cum[0] == 0, cum[i+1] == cum[i] + c[i], sum(c) == total_freq")
 
     @classmethod
     def from_counts(cls, counts, target_total=65536, ctx=None):
@@ -738,6 +739,52 @@ class Wide16StaticModel(WideStaticModel):
         d["dec_symof_bytes"] = 2 << d["dec_symof_bits"]
         d["dec_row_bytes"] = 4 * (self.n_symbols + 2)
         return d
+
+
+class Wide16FineModel(Wide16StaticModel):
+    """rc_model_create_static_wide16_fine: a wide16 static model whose total lies above 65536, up
+    to 2^24, so that a table over thousands of rare symbols, or over all 65536 with every one
+    encodable, still tells them apart.  The wide16 batch calls and chunk helpers take it as they
+    take a Wide16StaticModel, with the same contract; a table whose total is at most 65536 is a
+    Wide16StaticModel's and is refused here (ValueError), so each table has one class.
+
+    The table is validated on the host at construction (ValueError); the device tables are made
+    on first use, so a model can be built and inspected without a device."""
+    _CHECK = "rc_model_wide16_fine_check_"
+    _CREATE = "rc_model_create_static_wide16_fine"
+    _WHAT = "wide16 fine"
+    _TOTALS = "65537..16777216"
+
+    @classmethod
+    def from_counts(cls, counts, target_total=1 << 20, ctx=None):
+        """A histogram scaled to target_total (65537..2^24) with every symbol kept encodable
+        (rc_quantize_counts_wide16_fine with RC_Q_ALL_SYMBOLS)."""
+        from .model_build import quantize_counts_wide16_fine
+        c, cum, total = quantize_counts_wide16_fine(counts, target_total, all_symbols=True)
+        return cls(c, cum, total, ctx=ctx)
+
+    def plan(self):
+        """rc_model_wide16_fine_plan_: what the launchers use for this table, as a dict."""
+        out = (ctypes.c_uint32 * 8)()
+        N.check(N.load().rc_model_wide16_fine_plan_(self.n_symbols, self.total, out),
+                "rc_model_wide16_fine_plan_")
+        keys = ("enc_lanes", "enc_lds", "enc_layout", "enc_table_bytes", "dec_lanes", "dec_lds",
+                "dec_bucket_bits", "dec_shift")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d["dec_bucket_bytes"] = (2 << d["dec_bucket_bits"]) + 4  # (with the sentinel)
+        n_occ = int(np.count_nonzero(self.c))
+        d["dec_occ_bytes"] = 2 * (n_occ + (n_occ & 1))
+        d["dec_rcum_bytes"] = 4 * (n_occ + 2)
+        return d
+
+    def max_bits_per_symbol(self):
+        """The bits to plan a slot with (slot_capacity): the costliest symbol's ideal
+        log2(total / c_min), up to 24, and 1/8 bit for what the coder loses at these totals: the
+        rounding of range / total (under 2^-23 bit) and range_reduction_expansion (1.44 bits on
+        average on fewer than one symbol in 256: under 0.006 bit).  It is no hard bound: one
+        symbol can settle 11 bytes (include/range_coder.h), and a slot that is too small is
+        RC_F_CAPACITY with the exact length, which encode_chunks_wide16 encodes again."""
+        return WideStaticModel.max_bits_per_symbol(self) + 0.125
 
 
 # ----------------------------------------------------------------------------- batch API
@@ -1106,7 +1153,7 @@ def decode_batch_wide(model, code, code_off, code_len, syms_out, sym_off, flags=
 
 def encode_batch_wide16(model, syms, sym_off, out, out_off, out_len=None, flags=None):
     """rc_encode_batch_wide16 on torch tensors (async on torch's current stream):
-    encode_batch_wide against a Wide16StaticModel (up to 65536 symbols).
+    encode_batch_wide against a Wide16StaticModel or a Wide16FineModel (up to 65536 symbols).
     Returns (out_len, flags)."""
     return _encode_batch("rc_encode_batch_wide16", model, syms, None, sym_off, out, out_off,
                          out_len, flags, wide=True)
@@ -1114,19 +1161,21 @@ def encode_batch_wide16(model, syms, sym_off, out, out_off, out_len=None, flags=
 
 def decode_batch_wide16(model, code, code_off, code_len, syms_out, sym_off, flags=None):
     """rc_decode_batch_wide16 on torch tensors (async on torch's current stream):
-    decode_batch_wide against a Wide16StaticModel.  Returns flags."""
+    decode_batch_wide against a Wide16StaticModel or a Wide16FineModel.  Returns flags."""
     return _decode_batch("rc_decode_batch_wide16", model, code, code_off, code_len, None,
                          syms_out, sym_off, flags, wide=True)
 
 
 def encode_chunks_wide16(model, chunks, raise_on_error=True):
-    """encode_chunks_wide against a Wide16StaticModel.  Returns a list of bytes."""
+    """encode_chunks_wide against a Wide16StaticModel or a Wide16FineModel.  Returns a list of
+    bytes."""
     return _encode_chunks(encode_batch_wide16, model, [_u16_chunk(c) for c in chunks], None,
                           raise_on_error)
 
 
 def decode_chunks_wide16(model, codes, counts, raise_on_error=True):
-    """decode_chunks_wide against a Wide16StaticModel.  Returns a list of uint16 arrays."""
+    """decode_chunks_wide against a Wide16StaticModel or a Wide16FineModel.  Returns a list of
+    uint16 arrays."""
     return _decode_chunks(decode_batch_wide16, model, codes, counts, None, raise_on_error,
                           wide=True)
 

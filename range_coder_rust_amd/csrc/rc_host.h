@@ -10,6 +10,7 @@
 #include "rc_order1.h"
 #include "rc_wide.h"
 #include "rc_wide16.h"
+#include "rc_wide16_fine.h"
 #include "rc_chunk_set.h"
 
 struct rc_ctx {
@@ -45,6 +46,8 @@ struct rc_model {
   WidePlan wplan;
   Wide16Args w16;  // kind 6, a wide16 static model (rc_wide16.h): `w16` and `w16plan`
   Wide16Plan w16plan;
+  Wide16FineArgs w16f;  // kind 6 with w16_fine: a wide16 fine model (rc_wide16_fine.h): `w16f` and
+  bool w16_fine;        // `w16plan`; the wide16 batch calls launch its kernels
   ChunkSetArgs cset;  // kind 5, a static chunk set (rc_chunk_set.h): `args` is row 0's
   O1Args o1;  // kind 4 (o1.period: 1, 2, 4 or 8)
   u32 o1_lag;  // kind 4: 1, 2, 4 or 8 (rc_order1.h: no field of the kernels' O1Args)

@@ -57,6 +57,7 @@ __global__ __launch_bounds__(WG) void k_synth_generic(u64 seed, const uint8_t* _
 #include <vector>
 
 #include "rc_wide16_tables.h"
+#include "rc_wide16_fine_tables.h"
 
 // The only place the library reads its environment (tests/test_abi.py checks that no other
 // source calls getenv): once per context, in rc_ctx_create.
@@ -1316,6 +1317,12 @@ rc_status rc_encode_batch_wide16(rc_ctx* ctx, const rc_model* wide16, const void
   return batch_call(ctx, wide16, 1u << RC_KIND_WIDE16, ((uintptr_t)syms & 1u) == 0, n_chunks,
                     syms && sym_off && out && out_off && out_len && flags,
                     "wide16 encode launch", [&] {
+                      if (wide16->w16_fine)
+                        return rc_wide16_fine_encode_launch(ctx->cur, ctx->knobs, wide16->w16f,
+                                                            wide16->div, wide16->w16plan,
+                                                            (const uint16_t*)syms, sym_off,
+                                                            n_chunks, out, out_off, out_len,
+                                                            flags);
                       return rc_wide16_encode_launch(ctx->cur, ctx->knobs, wide16->w16,
                                                      wide16->div, wide16->w16plan,
                                                      (const uint16_t*)syms, sym_off, n_chunks,
@@ -1330,11 +1337,93 @@ rc_status rc_decode_batch_wide16(rc_ctx* ctx, const rc_model* wide16, const uint
   return batch_call(ctx, wide16, 1u << RC_KIND_WIDE16, ((uintptr_t)syms_out & 1u) == 0,
                     n_chunks, code && code_off && code_len && syms_out && sym_off && flags,
                     "wide16 decode launch", [&] {
+                      if (wide16->w16_fine)
+                        return rc_wide16_fine_decode_launch(ctx->cur, ctx->knobs, wide16->w16f,
+                                                            wide16->div, wide16->w16plan, code,
+                                                            code_off, code_len,
+                                                            (uint16_t*)syms_out, sym_off,
+                                                            n_chunks, flags);
                       return rc_wide16_decode_launch(ctx->cur, ctx->knobs, wide16->w16,
                                                      wide16->div, wide16->w16plan, code, code_off,
                                                      code_len, (uint16_t*)syms_out, sym_off,
                                                      n_chunks, flags);
                     });
+}
+
+}  // extern "C"
+
+// ---- wide16 fine models (rc_wide16_fine.h; kernels in rc_wide16_fine.hip) ----
+
+// what rc_model_create_static_wide16_fine accepts (include/range_coder.h)
+static rc_status wide16_fine_check(u32 n_symbols, const u32* c, const u32* cum, u32 total) {
+  if (!c || !cum) return RC_E_ARG;
+  if (n_symbols < 1 || n_symbols > RC_MAX_WIDE16_SYMBOLS || total <= 65536u ||
+      total > RC_MAX_WIDE16_FINE_TOTAL)
+    return RC_E_BAD_MODEL;
+  return table_ok(n_symbols, c, cum, total) ? RC_OK : RC_E_BAD_MODEL;
+}
+
+extern "C" {
+
+// Internal test hooks (not in include/range_coder.h; host only, no device needed).
+// rc_model_wide16_fine_check_: rc_model_create_static_wide16_fine's validation of its table.
+rc_status rc_model_wide16_fine_check_(uint32_t n_symbols, const uint32_t* c_freq,
+                                      const uint32_t* cum_freq, uint32_t total_freq) {
+  return wide16_fine_check(n_symbols, c_freq, cum_freq, total_freq);
+}
+// rc_model_wide16_fine_plan_: what the launchers use for a table of n_symbols symbols and total
+// total_freq, out[8] = encoder {lanes per workgroup, dynamic LDS bytes (rings only), 0, bytes of
+// the entries in device memory}, decoder {lanes, LDS bytes, log2 of the bucket count, the bucket
+// shift}.
+rc_status rc_model_wide16_fine_plan_(uint32_t n_symbols, uint32_t total_freq, uint32_t* out) {
+  if (!out) return RC_E_ARG;
+  Wide16Plan p;
+  rc_wide16_fine_plan(n_symbols, total_freq, &p);
+  if (!p.enc_lanes) return RC_E_BAD_MODEL;
+  const u32 v[8] = {p.enc_lanes, p.enc_lds, p.enc_layout, p.enc_tab,
+                    p.dec_lanes, p.dec_lds, p.dec_bits,   p.dec_shift};
+  memcpy(out, v, sizeof v);
+  return RC_OK;
+}
+
+rc_status rc_model_create_static_wide16_fine(rc_ctx* ctx, uint32_t n_symbols,
+                                             const uint32_t* c_freq, const uint32_t* cum_freq,
+                                             uint32_t total_freq, rc_model** out) {
+  if (!ctx || !c_freq || !cum_freq || !out) return RC_E_ARG;
+  *out = nullptr;
+  const rc_status ok = wide16_fine_check(n_symbols, c_freq, cum_freq, total_freq);
+  if (ok != RC_OK) return ok;
+  Wide16Plan plan;
+  rc_wide16_fine_plan(n_symbols, total_freq, &plan);
+  const Wide16FineTables t =
+      wide16_fine_build_tables(n_symbols, c_freq, cum_freq, total_freq, plan.dec_bits);
+  // (the 8-B entries first: the allocation's alignment is theirs; then the 4-B cum row, then the
+  // halfwords, the occupied symbols an even count so that the buckets stay 4-B aligned)
+  const size_t enc_bytes = t.enc.size() * sizeof(u32), rcum_bytes = t.rcum.size() * sizeof(u32),
+               occ_bytes = t.occ.size() * sizeof(uint16_t),
+               bucket_bytes = t.bucket.size() * sizeof(uint16_t);
+  rc_model* mm = nullptr;
+  char* d = nullptr;
+  const rc_status up = model_upload(ctx, RC_KIND_WIDE16, total_freq,
+                                    {{t.enc.data(), enc_bytes},
+                                     {t.rcum.data(), rcum_bytes},
+                                     {t.occ.data(), occ_bytes},
+                                     {t.bucket.data(), bucket_bytes}},
+                                    &mm, &d);
+  if (up != RC_OK) return up;
+  mm->w16plan = plan;
+  mm->w16_fine = true;
+  Wide16FineArgs& a = mm->w16f;
+  small_model_args(a.m, n_symbols, total_freq, plan.dec_bits, plan.dec_shift);
+  a.enc = (const uint2*)d;
+  a.rcum = (const u32*)(d + enc_bytes);
+  a.occ = (const uint16_t*)(d + enc_bytes + rcum_bytes);
+  a.bucket = (const uint16_t*)(d + enc_bytes + rcum_bytes + occ_bytes);
+  a.enc_clamp = t.enc_clamp;
+  a.shift = t.shift;
+  a.qmax = total_freq - 1u;
+  *out = mm;
+  return RC_OK;
 }
 
 }  // extern "C"

@@ -1125,8 +1125,8 @@ rc_status rc_ideal_bits_wide(rc_ctx* ctx, const rc_model* wide, const void* syms
 
 }  // extern "C"
 
-// rc_quantize_counts / rc_quantize_counts_wide / rc_quantize_counts_wide16: one rule, alphabets
-// of up to max_symbols
+// rc_quantize_counts / rc_quantize_counts_wide / rc_quantize_counts_wide16 /
+// rc_quantize_counts_wide16_fine: one rule, alphabets of up to max_symbols
 static rc_status quantize_counts(const uint64_t* counts, uint32_t n_symbols, u32 max_symbols,
                                  uint64_t target_total, uint32_t qflags, uint32_t* c_out,
                                  uint32_t* cum_out, uint32_t* total_out) {
@@ -1213,6 +1213,15 @@ rc_status rc_quantize_counts_wide16(const uint64_t* counts, uint32_t n_symbols,
                                     uint32_t* cum_out, uint32_t* total_out) {
   // every symbol kept encodable needs a frequency of its own: no target below n can hold them
   if ((qflags & RC_Q_ALL_SYMBOLS) && target_total && n_symbols > target_total) return RC_E_ARG;
+  return quantize_counts(counts, n_symbols, RC_MAX_WIDE16_SYMBOLS, target_total, qflags, c_out,
+                         cum_out, total_out);
+}
+
+rc_status rc_quantize_counts_wide16_fine(const uint64_t* counts, uint32_t n_symbols,
+                                         uint64_t target_total, uint32_t qflags, uint32_t* c_out,
+                                         uint32_t* cum_out, uint32_t* total_out) {
+  // the fine models' totals: above 2^16 (a smaller one is rc_quantize_counts_wide16's), at most 2^24
+  if (target_total <= 65536u || target_total > RC_MAX_WIDE16_FINE_TOTAL) return RC_E_ARG;
   return quantize_counts(counts, n_symbols, RC_MAX_WIDE16_SYMBOLS, target_total, qflags, c_out,
                          cum_out, total_out);
 }

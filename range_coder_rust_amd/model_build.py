@@ -28,6 +28,7 @@ examples/sample_impl.rs:49-60) and scanning (calc_cum, :61-69); PModel::ideal_co
   build_wide_model(syms, sym_off, n)         those counts -> WideStaticModel, in one call
   histogram16(syms, sym_off)                 the exact 65536-bin histogram of 16-bit symbols (HIP)
   build_wide16_model(syms, sym_off)          those counts -> Wide16StaticModel, in one call
+                                             (target_total > 65536: a Wide16FineModel)
   ideal_bits_wide(model, syms, sym_off)      rc_ideal_bits_wide: per-chunk ideal bits of a wide
                                   model, straight from the symbols (HIP)
   cost_table(c, total)            rc_cost_table: a row's integer costs, 2^-16 bit units (host)
@@ -42,7 +43,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from .api import (ChunkModelSet, Order1ModelSet, StaticModel, Wide16StaticModel, WideStaticModel, _check_dev, _ptr, _sym16, _torch,
+from .api import (ChunkModelSet, Order1ModelSet, StaticModel, Wide16FineModel, Wide16StaticModel, WideStaticModel, _check_dev, _ptr, _sym16, _torch,
                   default_context)
 
 
@@ -80,6 +81,15 @@ def quantize_counts_wide16(counts, target_total=0, all_symbols=False):
     if all_symbols and target_total and len(counts) > target_total:
         raise ValueError("all_symbols needs target_total >= the number of symbols")
     return quantize_counts(counts, target_total, all_symbols, _entry="rc_quantize_counts_wide16")
+
+
+def quantize_counts_wide16_fine(counts, target_total=1 << 20, all_symbols=False):
+    """rc_quantize_counts_wide16_fine (host): quantize_counts for wide16 fine models (len n <=
+    65536, 65536 < target_total <= 2^24; any other target is a ValueError)."""
+    if not 65536 < int(target_total) <= N.MAX_WIDE16_FINE_TOTAL:
+        raise ValueError("a wide16 fine model's target_total lies in 65537..16777216")
+    return quantize_counts(counts, target_total, all_symbols,
+                           _entry="rc_quantize_counts_wide16_fine")
 
 
 def histogram(syms, sym_off, per_chunk=False, batch=True, ctx=None):
@@ -475,7 +485,8 @@ def histogram16(syms, sym_off, ctx=None):
 
 
 def build_wide16_model(syms, sym_off, n_symbols=None, target_total=1 << 16, ctx=None):
-    """histogram16 of the batch, then a Wide16StaticModel of its table scaled to target_total over
+    """histogram16 of the batch, then a Wide16StaticModel of its table scaled to target_total (a
+    Wide16FineModel when target_total lies above 65536, up to 2^24) over
     n_symbols symbols (None: the largest symbol that occurs, plus one).  Every symbol that occurs
     gets c >= 1; one that does not may get 0 and is then not encodable.  Raises ValueError when a
     symbol >= n_symbols occurs, when nothing occurs, or when more distinct symbols occur than
@@ -493,6 +504,10 @@ def build_wide16_model(syms, sym_off, n_symbols=None, target_total=1 << 16, ctx=
         raise ValueError(f"symbol {int(used[-1])} >= n_symbols in the data")
     if target_total and used.size > target_total:
         raise ValueError(f"{used.size} distinct symbols occur: more than target_total")
+    if target_total and target_total > 65536:  # a fine model's total
+        c, cum, total = quantize_counts_wide16_fine(counts[:n_symbols], target_total,
+                                                    all_symbols=False)
+        return Wide16FineModel(c, cum, total, ctx=ctx)
     c, cum, total = quantize_counts_wide16(counts[:n_symbols], target_total, all_symbols=False)
     return Wide16StaticModel(c, cum, total, ctx=ctx)
 

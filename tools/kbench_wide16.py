@@ -14,6 +14,15 @@ wide coder at n = 4096 on the same symbols (the price of moving the table out of
 -DRC_WIDE16_STATS (RC_LIB_PATH) adds the share of wave-symbols that took the decoder's fix-up.
 Prints one JSON line per run; --out also writes them as a JSON list.
 
+--fine: after each wide16 run, the same symbols through wide16 fine models of the same Zipf weights
+quantised to totals 2^17, 2^20 and 2^24, in the same process, so that each rate's ratio to the
+wide16 coders at total 2^16 is a same-run ratio.  A scratch build with -DRC_WIDE16_FINE_STATS adds
+the shares of wave-symbols that ran the decoder's rank search and its fix-up.
+
+--dense: int16 Laplace(b = 1500) samples and fp16 bit patterns of standard normals, 2^26 symbols in
+2^12 chunks: code bytes and rates under build_wide16_model at totals 2^16 (wide16), 2^20 and 2^24
+(fine), beside the ideal bits numpy gives for the same tables.  A report.
+
 --bf16: float32 normals cast to bf16 bit patterns, 2^26 symbols in 2^12 chunks: the code bytes and
 the rates of build_wide16_model + the wide16 coders against the route such data had before, the
 same bytes through fit_order1_set(period=2, n_models=8) and the order-1 coders.  A report."""
@@ -33,7 +42,12 @@ sys.path.insert(0, ROOT)
 def zipf_table(rc, n, total=65536):
     w = 1.0 / np.arange(1, n + 1, dtype=np.float64) ** 1.2
     counts = np.maximum(1, np.round(w / w.sum() * 1e12)).astype(np.uint64)
+    if total > 65536:
+        return rc.quantize_counts_wide16_fine(counts, total, all_symbols=True)
     return rc.quantize_counts_wide16(counts, total, all_symbols=True)
+
+
+FINE_TOTALS = (1 << 17, 1 << 20, 1 << 24)
 
 
 def timed(torch, a, enc, dcd, fe, fd, ol, src, dst, n_sym, sym_bytes, extra):
@@ -71,7 +85,8 @@ def bench_zipf(a, torch, rc, ctx):
     syms = torch.empty(n * L, dtype=torch.int16, device=dev)
     dec = torch.empty(n * L, dtype=torch.int16, device=dev)
     so = torch.arange(n + 1, dtype=torch.int64, device=dev) * L
-    cap = rc.slot_capacity(L, 16.0, slack=1.02)  # (every c >= 1 of 65536: 16 bits at most)
+    # (every c >= 1 of 65536: 16 bits at most; of 2^24: 24 and the fine models' allowance)
+    cap = rc.slot_capacity(L, 24.125 if a.fine else 16.0, slack=1.02)
     out = torch.empty(n * cap, dtype=torch.uint8, device=dev)
     oo = torch.arange(n + 1, dtype=torch.int64, device=dev) * cap
     co = oo[:-1].contiguous()
@@ -137,6 +152,83 @@ def bench_zipf(a, torch, rc, ctx):
                           ("n_symbols", "fixup_wave_symbol_share")}), flush=True)
         results.append(r)
         w16.close()
+        if a.fine:
+            results += bench_fine(a, rc, ctx, ns, r, run, syms, dec, so, out, oo, co, ol, fe, fd)
+    return results
+
+
+def bench_fine(a, rc, ctx, ns, w16_res, run, syms, dec, so, out, oo, co, ol, fe, fd):
+    """The symbols the wide16 run just coded, through fine models of the same weights."""
+    stats = getattr(ctx._lib, "rc_wide16_fine_stats_read_", None)
+    st = (ctypes.c_uint64 * 3)()
+    res = []
+    for total in FINE_TOTALS:
+        c, cum, t = zipf_table(rc, ns, total)
+        fm = rc.Wide16FineModel(c, cum, t, ctx=ctx)
+        dec.zero_()
+        if stats is not None:
+            stats(st)  # (reading clears the counters)
+        r = run("wide16_fine", lambda: rc.encode_batch_wide16(fm, syms, so, out, oo, ol, fe),
+                lambda: rc.decode_batch_wide16(fm, out, co, ol, dec, so, fd), syms, dec, 2,
+                dict(n_symbols=ns, plan=fm.plan()))
+        r["table_total"] = total
+        if stats is not None and stats(st) == 0 and st[0]:
+            r["search_wave_symbol_share"] = round(st[1] / st[0], 6)
+            r["fixup_wave_symbol_share"] = round(st[2] / st[0], 6)
+        r["encode_vs_wide16"] = round(r["encode_gsym_s"] / w16_res["encode_gsym_s"], 4)
+        r["decode_vs_wide16"] = round(r["decode_gsym_s"] / w16_res["decode_gsym_s"], 4)
+        r["bytes_per_symbol_wide16"] = w16_res["bytes_per_symbol"]
+        print(json.dumps({k: v for k, v in r.items() if "_vs_" in k or "share" in k or k in
+                          ("n_symbols", "table_total", "bytes_per_symbol",
+                           "bytes_per_symbol_wide16")}), flush=True)
+        res.append(r)
+        fm.close()
+    return res
+
+
+def bench_dense(a, torch, rc, ctx):
+    """Dense 16-bit sources: the code under tables of total 2^16, 2^20 and 2^24."""
+    dev = torch.device("cuda", 0)
+    n, L = 1 << 12, 1 << 14
+    g = torch.Generator(device=dev).manual_seed(0xDE75E)
+    so = torch.arange(n + 1, dtype=torch.int64, device=dev) * L
+    cap = rc.slot_capacity(L, 18.0, slack=1.02)
+    out = torch.empty(n * cap, dtype=torch.uint8, device=dev)
+    oo = torch.arange(n + 1, dtype=torch.int64, device=dev) * cap
+    co = oo[:-1].contiguous()
+    ol = torch.zeros(n, dtype=torch.int64, device=dev)
+    fe = torch.zeros(n, dtype=torch.int32, device=dev)
+    fd = torch.zeros(n, dtype=torch.int32, device=dev)
+    results = []
+    for data in ("int16 Laplace(b=1500)", "fp16 bits of N(0,1)"):
+        if data.startswith("int16"):
+            u = torch.rand(n * L, device=dev, generator=g, dtype=torch.float64) - 0.5
+            x = -1500.0 * torch.sign(u) * torch.log1p(-2.0 * u.abs())
+            syms = x.round().clamp_(-32768, 32767).to(torch.int16)
+            del u, x
+        else:
+            x = torch.randn(n * L, device=dev, generator=g, dtype=torch.float32)
+            syms = x.to(torch.float16).view(torch.int16)
+            del x
+        counts = rc.histogram16(syms, so, ctx=ctx).cpu().numpy().astype(np.float64)
+        nz = counts > 0
+        entropy = float(-(counts[nz] / counts.sum() * np.log2(counts[nz] / counts.sum())).sum())
+        dec = torch.empty_like(syms)
+        for total in (1 << 16, 1 << 20, 1 << 24):
+            m = rc.build_wide16_model(syms, so, target_total=total, ctx=ctx)
+            cm = m.c.astype(np.float64)
+            ideal = float((counts[:len(cm)][cm > 0] * np.log2(total / cm[cm > 0])).sum())
+            dec.zero_()
+            results.append(timed(
+                torch, a, lambda: rc.encode_batch_wide16(m, syms, so, out, oo, ol, fe),
+                lambda: rc.decode_batch_wide16(m, out, co, ol, dec, so, fd), fe, fd, ol, syms, dec,
+                n * L, 2, dict(coder=type(m).__name__, data=data, chunks=n, chunk_symbols=L,
+                               table_total=total, n_symbols=m.n_symbols,
+                               distinct_symbols=int(nz.sum()), entropy_bits=round(entropy, 4),
+                               ideal_bits_per_symbol=round(ideal / (n * L), 4),
+                               ideal_bytes=int(np.ceil(ideal / 8)))))
+            m.close()
+        del syms, dec
     return results
 
 
@@ -205,12 +297,15 @@ def main():
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--bf16", action="store_true")
+    p.add_argument("--fine", action="store_true")
+    p.add_argument("--dense", action="store_true")
     p.add_argument("--out", default=None)
     a = p.parse_args()
     import torch
     import range_coder_rust_amd as rc
     ctx = rc.default_context(0)
-    results = bench_bf16(a, torch, rc, ctx) if a.bf16 else bench_zipf(a, torch, rc, ctx)
+    results = (bench_bf16(a, torch, rc, ctx) if a.bf16 else bench_dense(a, torch, rc, ctx)
+               if a.dense else bench_zipf(a, torch, rc, ctx))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -33,11 +33,13 @@ A third of the iterations instead draw one of:
               in 257 .. 65536, total in [256, 2^16], dense or with runs of zero frequencies,
               1 .. 1500 ragged chunks of 16-bit symbols, against orc_stream_encode fed each
               symbol's triple chunk by chunk, and the round trip
+  wide16_fine a wide16 fine model (rc_model_create_static_wide16_fine): the wide16 draw with the
+              total log-uniform in 65537 .. 2^24 (2^24 - 3, 2^24, 2^20 and 65537 now and then)
 Prints a progress line per iteration and one JSON summary line; exits 1 at the first mismatch
 (after printing what differed).  The oracle is the checker here, never the thing measured.
 
 Usage (GPU box): python3 tools/parity_soak.py [seconds] [seed] [draw]
-(draw: only this one of adaptive, stream-enc, stream-dec, chunk-set, wide16)
+(draw: only this one of adaptive, stream-enc, stream-dec, chunk-set, wide16, wide16_fine)
 """
 import json
 import math
@@ -329,9 +331,13 @@ def chunk_set_iteration(rng):
     return (f"chunk-set K={K} total={total} chunks={n}", n, int(lens.sum()), int(g_len.sum()), bad)
 
 
-def wide16_iteration(rng):
+def wide16_iteration(rng, fine=False):
     n_sym = int(round(math.exp(rng.uniform(math.log(257), math.log(65536)))))
-    total = int(rng.choice([256, 4096, 65535, 65536, int(rng.integers(256, 65537))]))
+    if fine:  # a wide16 fine model: the total log-uniform in 65537 .. 2^24, its ends now and then
+        total = int(rng.choice([65537, (1 << 24) - 3, 1 << 24, 1 << 20, int(round(math.exp(
+            rng.uniform(math.log(65537), math.log(1 << 24)))))], p=[.1, .1, .1, .1, .6]))
+    else:
+        total = int(rng.choice([256, 4096, 65535, 65536, int(rng.integers(256, 65537))]))
     p = rng.random(n_sym) ** 6 + 1e-6
     live = min(n_sym, total, int(rng.choice([n_sym, max(1, n_sym // 7),
                                              int(rng.integers(1, n_sym + 1))])))
@@ -343,7 +349,8 @@ def wide16_iteration(rng):
         p = q
     c = quantise(p, total, rng).astype(np.uint32)
     cum = np.concatenate([[0], np.cumsum(c.astype(np.uint64))[:-1]]).astype(np.uint32)
-    m = rc.Wide16StaticModel(c, cum, total)
+    m = (rc.Wide16FineModel if fine else rc.Wide16StaticModel)(c, cum, total)
+    what = "wide16_fine" if fine else "wide16"
     n = int(rng.choice([1, 2, 255, 256, 257, 1024, int(rng.integers(1, 1501))]))
     lens = rng.choice([0, 1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 300, 1000], n).astype(np.int64)
     occupied = np.flatnonzero(c)
@@ -371,14 +378,18 @@ def wide16_iteration(rng):
         f, want, _ = cpu.stream_encode(cpu.Stream.fresh(), tri.astype(np.uint32), finish=True)
         a, L = int(out_off[k]), len(want)
         if f != int(g_fe[k]) or L != int(g_len[k]) or bytes(g_out[a:a + L]) != want:
-            bad.append(f"wide16 encode of chunk {k}")
+            bad.append(f"{what} encode of chunk {k}")
             break
         if g_fd[k] != 0 or not np.array_equal(g_dec[sym_off[k]:sym_off[k + 1]], sk):
-            bad.append(f"wide16 decode of chunk {k}")
+            bad.append(f"{what} decode of chunk {k}")
             break
     m.close()
-    return (f"wide16 n={n_sym} live={live} total={total} chunks={n}", n, int(lens.sum()),
+    return (f"{what} n={n_sym} live={live} total={total} chunks={n}", n, int(lens.sum()),
             int(g_len.sum()), bad)
+
+
+def wide16_fine_iteration(rng):
+    return wide16_iteration(rng, fine=True)
 
 
 def main():
@@ -387,7 +398,8 @@ def main():
     only = {"adaptive": adaptive_iteration, "stream-enc": stream_enc_iteration,
             "stream-dec": stream_dec_iteration,
             "chunk-set": chunk_set_iteration,
-            "wide16": wide16_iteration}[sys.argv[3]] if len(sys.argv) > 3 else None
+            "wide16": wide16_iteration,
+            "wide16_fine": wide16_fine_iteration}[sys.argv[3]] if len(sys.argv) > 3 else None
     rng = np.random.default_rng(seed)
     rc.default_context(0)
     t_end = time.time() + budget
@@ -395,11 +407,12 @@ def main():
     kinds = {}
     while time.time() < t_end:
         other = rng.random()
-        if other < 0.35 or only:
+        if other < 0.37 or only:  # (0.35 .. 0.37: the wide16_fine draw)
             fn = only or (adaptive_iteration if other < 0.1 else
                           stream_enc_iteration if other < 0.175 else
                           stream_dec_iteration if other < 0.25 else
-                          chunk_set_iteration if other < 0.31 else wide16_iteration)
+                          chunk_set_iteration if other < 0.31 else
+                          wide16_iteration if other < 0.35 else wide16_fine_iteration)
             name, n, nsym, nbytes, bad = fn(rng)
             it += 1
             chunks += n
