@@ -19,6 +19,9 @@
  *  - Batch calls are asynchronous and stream-ordered on the context's stream.
  *  - Offsets: chunk k's symbols are sym[sym_off[k] .. sym_off[k+1]) (n_chunks+1 entries,
  *    non-decreasing, any alignment).  Encoder output slot k is out[out_off[k] .. out_off[k+1]).
+ *    Offsets are full 64-bit element indices (symbols, rows, triples or bytes, as the call
+ *    says); arenas beyond 4 GiB, with byte offsets and element indices past 2^32, are covered
+ *    by the suite for every batch call (tests/test_gpu_high_offsets.py).
  */
 #ifndef RANGE_CODER_AMD_H
 #define RANGE_CODER_AMD_H
